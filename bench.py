@@ -2,8 +2,17 @@
 """Benchmark: halfspace-constraints/sec of the DR-CVaR safe-halfspace engine (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does only what the headline figure needs: it draws the batch, warms up, times the K
+steps, writes the last step's records if `--dump-outputs DIR` is given (DIR/records.npy, float64
+[O, T, 8]; the inputs are seeded, so two builds can be compared record for record) and prints the
+metric line with the `roofline` block that follows from the same timed region.  Everything that
+takes runs of its own — the strong-scaling legs, the large-batch and replicated rooflines, the
+sampler, the MPC hand-off, the CPU baselines and the comparison with the oracle — is behind
+`--full`.
 
 A step = one evaluation of the hot path over one batch: every (obstacle, horizon-step) unit of a
 synthetic [O, T, N, 2] fp64 sample tensor -> mean / CVaR / DR-CVaR halfspaces, i.e. ONE launch
@@ -28,6 +37,7 @@ read; c5 adds the full loop with the QP.
 Prints ONE JSON line on rank 0: value = units of all ranks / max rank time, plus
   roofline        the kernel on this workload: algorithmic bytes per launch / average launch time
                   (N=1: HIP events over the timed region / K, launch gaps included)
+and with `--full` (null otherwise):
   strong_scaling  {c4, c5}: global batch sharded over N ranks (+ all-gather), phase splits
   roofline_large  (N=1) the kernel on the resident 2 GB C5 batch, graph-replayed, event-timed
   roofline_c3_replicated  (N=1) the C3 launch plan over C3 replicated to a 2 GB working set
@@ -326,6 +336,20 @@ def timed(world, fn, dev, stream):
     return elapsed, ev_s, res
 
 
+def dump_outputs(directory, sb, world, rank):
+    """--dump-outputs: the records the timed path left after its last step — what a caller of
+    the launch receives, float64 [O, T, 8] (12.8 KB for C3, 819 KB for C5) — as
+    DIR/records.npy; at N > 1 every rank writes the block it evaluated as records_rank<r>.npy
+    (the metric line's step has no exchange)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    if world == 1:
+        name, rec = "records.npy", sb.records()
+    else:
+        name, rec = f"records_rank{rank}.npy", sb.local_records()
+    np.save(os.path.join(directory, name), rec.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -334,6 +358,13 @@ def main():
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--launch", default="graph", choices=["graph", "eager"])
     ap.add_argument("--graph-batch", type=int, default=50)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the records of the last timed step to "
+                         "DIR/records.npy (float64 [O, T, 8]; records_rank<r>.npy per rank at N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the metric line's timed steps also run everything else: the strong-scaling "
+                         "legs, the large-batch and replicated rooflines, the sampler, the MPC hand-off, the "
+                         "CPU baselines and the comparison with the oracle (the --no-* options trim it)")
     ap.add_argument("--strong-workloads", default="c4,c5",
                     help="global batches of the strong-scaling legs (sharded over the ranks), comma-separated")
     ap.add_argument("--strong-steps", type=int, default=20)
@@ -392,11 +423,15 @@ def main():
     stepper = Stepper(sb, mode, args.graph_batch, args.steps, dev, exchange=False, warmup=args.warmup,
                       world=world, ctrl=ctrl)
     stepper.run(args.warmup)                   # untimed warmup (W steps, the same launch path)
+    if args.dump_outputs:
+        sb.send.zero_()                        # what is dumped below was written by the timed steps
     elapsed, ev_s, K = timed(world, lambda: stepper.run(args.steps), dev, stream)
     kernel_s, ktiming = ev_s / K, "HIP events over the timed region / K (launch gaps included)"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sb, world, rank)
 
     strong = None
-    if not args.no_large and not args.no_strong:
+    if args.full and not args.no_large and not args.no_strong:
         strong = {w: strong_scaling(args, world, rank, dev, stream, params, gdev, mode, w, ctrl)
                   for w in args.strong_workloads.split(",") if w}
 
@@ -451,7 +486,7 @@ def main():
         result["roofline_c3_replicated"] = replicated
         result["mpc_handoff"] = mpc
         result["sampling"] = sampling
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             import numpy as np
             samples4 = sb.samples.view(O, T, N, 2)
             ref, base = cpu_baseline(samples4, ego, params, args.cpu_seconds)

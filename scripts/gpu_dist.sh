@@ -28,7 +28,7 @@ for n in ${RANKS:-2 4 8}; do
   extra=""
   [ "$n" = 4 ] && extra="--no-mpc"
   timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-    --master-port $((29500 + n)) bench.py --gpus $n --steps 400 --warmup 50 --dist-backend gloo $extra \
+    --master-port $((29500 + n)) bench.py --gpus $n --steps 400 --warmup 50 --dist-backend gloo --full $extra \
     --no-cpu-baseline > $OUT/dist_$n.log 2>&1 || { tail -30 $OUT/dist_$n.log; exit $n; }
   show $n $OUT/dist_$n.log
 done

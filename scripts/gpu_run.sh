@@ -4,7 +4,7 @@
 # limit; a failing step stops the script (nothing further touches the GPU in that call).
 #
 #   suite        pytest -m gpu (K="<expr>" narrows it)          smoke      __graft_entry__.smoke()
-#   bench20      the driver's command (bench_steps20.json)      bench      the default bench.py
+#   bench20      the driver's command (bench_steps20.json)      bench      bench.py --full
 #   mpc          scripts/mpc_bench.py on the product library, then on each VARIANTS=<a.so b.so>,
 #                interleaved ROUNDS=<n> times
 #   mpctests     the MPC GPU tests only (on DRCVAR_DIAG_LIB when LIB=<a.so> is given)
@@ -39,7 +39,7 @@ for s in "$@"; do
     bench20)
       timeout -k 10 600 $CMD > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err || { tail $OUT/bench_steps20.err; fail bench20; } ;;
     bench)
-      timeout -k 10 600 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail $OUT/bench_default.err; fail bench; } ;;
+      timeout -k 10 600 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail $OUT/bench_default.err; fail bench; } ;;
     mpc)
       for r in $(seq 1 ${ROUNDS:-1}); do
         timeout -k 10 300 python3 scripts/mpc_bench.py --shapes $MPC_SHAPES > $OUT/mpc_product_$r.log 2>&1 || fail mpc

@@ -1,4 +1,4 @@
-"""Re-solve a dumped QP hand-off problem (bench.py with DRCVAR_BENCH_DUMP_QP=<npz>) on the device
+"""Re-solve a dumped QP hand-off problem (bench.py --full with DRCVAR_BENCH_DUMP_QP=<npz>) on the device
 with several cluster sizes and both kernel forms, and print each answer's status, iterations,
 polish attempts and max |u - u_bench|; saves the answers to <npz>.resolved.npz for the CPU
 oracle / KKT check (scripts/micro/c5_qp_kkt.py)."""

@@ -1,7 +1,7 @@
 """Writes tests/golden/qp_c5_degenerate.npz: bench.py's C5 QP hand-off problem (256 obstacles x
 50 steps of device-computed DR-CVaR halfspaces from the round-3 device sampler, H = 50, the
 straight-line ego reference, input bounds +-5, position bounds +-10), dumped on the GPU box by
-``DRCVAR_BENCH_DUMP_QP=gpurun_out/c5qp.npz python bench.py`` (scripts/micro/gpu_c5qp.sh), with the
+``DRCVAR_BENCH_DUMP_QP=<dir>/c5qp.npz python bench.py --full``, with the
 oracle's answer.  On this instance the oracle's interior-point method stalls at merit ~4e-10 and
 its three guessed active sets all fail; the answer comes from its one-row-per-step active-set
 refinement (oracle/mpc_qp.py:_polish_steps), KKT-certified to ~1e-13.  Run once; output committed.
