@@ -161,21 +161,26 @@ class PeerExchange:
             _native.check(code)
 
     def prepare_launch(self, samples: torch.Tensor, ego: torch.Tensor, params: RiskParams, row_base: int,
-                       stream=None) -> engine.PreparedLaunch:
+                       stream=None, status: torch.Tensor | None = None) -> engine.PreparedLaunch:
         """Freeze one ``drcvar_safe_halfspaces_f64_peer`` call over an ``[O, T, N, 2]`` block whose
-        unit 0 is global row ``row_base``."""
+        unit 0 is global row ``row_base``.  ``status`` (optional int32, ``O * T`` elements) receives
+        each unit's ``_native.UNIT_*`` bits, as in :func:`engine.safe_halfspaces`."""
         params.validate()
         engine._check_samples(samples, 4)
         O, T, N, _ = samples.shape
         engine._check_pairs(ego, "ego", T, samples.device)
         if row_base < 0 or row_base + O * T > self.rows:
             raise ValueError(f"rows [{row_base}, {row_base + O * T}) outside the exchange's {self.rows}")
+        if status is not None:
+            engine._check_status(status, O * T, samples.device)
         args = (ctypes.c_void_p(samples.data_ptr()), O, T, N, samples.stride(0), samples.stride(1),
                 samples.stride(2), ctypes.c_void_p(ego.data_ptr()), ego.stride(0),
                 params.robot_radius, params.obstacle_radius, params.alpha, params.delta, params.epsilon,
-                self._launch_ref, int(row_base), ctypes.c_void_p(None),
+                self._launch_ref, int(row_base),
+                ctypes.c_void_p(status.data_ptr() if status is not None else None),
                 ctypes.c_void_p(engine._stream_handle(samples.device, stream)))
-        return engine.PreparedLaunch(self._lib.drcvar_safe_halfspaces_f64_peer, args, (samples, ego, self))
+        return engine.PreparedLaunch(self._lib.drcvar_safe_halfspaces_f64_peer, args,
+                                     (samples, ego, self, status))
 
     def generation(self) -> int:
         return int(self.state[0].item())
@@ -183,6 +188,16 @@ class PeerExchange:
     def error(self) -> int:
         """0, or bit 63 | bit j for every rank j whose flag a wait gave up on."""
         return int(self.state[2].item()) & 0xFFFFFFFFFFFFFFFF
+
+    def check(self) -> None:
+        """Raise if a wait ever gave up on a peer: ``out`` may then hold rows of an earlier step.
+        One host read of the error word (a synchronisation), so it is an explicit call — after a
+        step whose records matter, never inside the timed step itself."""
+        err = self.error()
+        if err:
+            silent = [j for j in range(self.world) if err >> j & 1]
+            raise RuntimeError(f"peer exchange on rank {self.rank}: a wait for rank(s) {silent} gave up at "
+                               f"its spin limit ({self.spin_limit_us} us); error word {err:#018x}")
 
     def close(self) -> None:
         """Collective: wait until this device and (a barrier on the control group) every peer
@@ -441,8 +456,13 @@ class ShardedBatch:
         self._launch = self.prepare()
 
     def prepare(self, stream=None) -> _Prepared:
-        """Frozen launches of this rank's block on ``stream`` (default: the current stream), one
-        per chunk — for hipGraph capture pass the capturing stream."""
+        """Frozen launches of this rank's block on ``stream`` (default: the stream current NOW,
+        resolved here once), one per chunk — for hipGraph capture pass the capturing stream.  The
+        returned object carries the stream, and :meth:`step` / :meth:`exchange` put the peer form's
+        publish/wait/copy launch on it: the kernel and that launch always share a stream, whatever
+        stream is current when they are issued."""
+        if stream is None and self.samples.device.type == "cuda":
+            stream = torch.cuda.current_stream(self.samples.device)
         launches = []
         for j in range(self.chunks):
             a, b = min(j * self.cs, self.count), min((j + 1) * self.cs, self.count)
@@ -504,6 +524,13 @@ class ShardedBatch:
         """Global ``[O, T, 8]`` records (after :meth:`step`; at world 1 the local block)."""
         src = self.full if self.full is not None else self.send
         return src[:self.U].view(self.O, self.T, engine.OUT_WIDTH)
+
+    def check_exchange(self) -> None:
+        """Raise ``RuntimeError`` if the peer exchange's error word is set (:meth:`PeerExchange.check`:
+        a wait gave up, ``records()`` may mix steps); no-op for the other exchanges.  An explicit call
+        with one host read — not part of :meth:`step` or :meth:`records`."""
+        if self.peer is not None:
+            self.peer.check()
 
     def close(self) -> None:
         """Collective for the peer exchange (see :meth:`PeerExchange.close`); no-op otherwise."""

@@ -1,11 +1,16 @@
-"""pytest on a variant build of the engine: python scripts/micro/pytest_variant.py <lib.so> <pytest args...>"""
+"""pytest on a variant build of the engine: python scripts/micro/pytest_variant.py <lib.so> <pytest args...>
+
+Tests that spawn worker processes (multiprocessing "spawn") re-import this file in every worker, so
+everything below the imports runs only as the main program; the workers of such tests choose their
+library themselves (DRCVAR_DIAG_LIB, e.g. tests/test_peer_exchange.py)."""
 import os
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd import _native  # noqa: E402
 
-_native.use_library(sys.argv[1])
-import pytest  # noqa: E402
+if __name__ == "__main__":
+    _native.use_library(sys.argv[1])
+    import pytest
 
-sys.exit(pytest.main(sys.argv[2:]))
+    sys.exit(pytest.main(sys.argv[2:]))

@@ -7,7 +7,8 @@ ever exercised with the C oracle injected).
 * `ShardedBatch` (per-rank device sampling of its units + the kernel writing into the all-gather
   input) gives, rank by rank, exactly the records of the whole batch;
 * a world-size-1 RCCL (`nccl`) process group runs `sharded_safe_halfspaces` and
-  `ShardedBatch.step` (launch + all_gather_into_tensor), eagerly and captured in a hipGraph.
+  `ShardedBatch.step` (launch + all_gather_into_tensor), eagerly and captured in a hipGraph, with
+  different records at every step (samples re-drawn / ego shifted in place).
 """
 import os
 import socket
@@ -106,27 +107,20 @@ def test_rccl_world1_sharded_safe_halfspaces(dev, rccl_group):
 
 def test_rccl_world1_sharded_batch_step_eager_and_graph(dev, rccl_group):
     """ShardedBatch with a (1-rank) RCCL group: the all-gather path runs (full buffer allocated),
-    eagerly and inside a captured hipGraph (launch + all_gather_into_tensor per step)."""
+    eagerly and inside a captured hipGraph (launch + all_gather_into_tensor per step).  Every step
+    has records of its own, as in tests/test_peer_exchange.py (`_exercise`): eager steps re-draw
+    the samples in place, captured steps shift the ego in place inside the graph (three steps per
+    graph, three replays, each step's output copied aside in the graph), `full` is NaN-filled
+    before every step and each step is compared bitwise with the plain launch of its inputs."""
+    from test_peer_exchange import GRAPH_STEPS, REPLAYS, _exercise
     O, T, N = 8, 10, 1000
     nominal, ego = _nominal(O, T, dev, seed=9)
     sb = sharding.ShardedBatch(nominal, ego, N, RiskParams(), 1, 0, group=rccl_group, seed=9,
                                force_exchange=True)
-    sb.full.fill_(float("nan"))
-    sb.step()
-    torch.cuda.synchronize()
-    whole_s, _ = synthetic.obstacle_batch(O, T, N, dev, seed=9)
-    want = engine.safe_halfspaces(whole_s, ego, RiskParams())
-    assert torch.equal(sb.records(), want)
-    sb.full.fill_(float("nan"))
-    g = torch.cuda.CUDAGraph()
-    cap = torch.cuda.Stream(dev)
-    with torch.cuda.graph(g, stream=cap):
-        launch = sb.prepare(torch.cuda.current_stream(dev))
-        for _ in range(3):
-            sb.step(launch)
-    g.replay()
-    torch.cuda.synchronize()
-    assert torch.equal(sb.records(), want)
+    assert sb.peer is None and sb.full is not None
+    fails, steps = _exercise(sb, nominal, ego, N, 9, dev, late=[None] * 3)
+    assert not fails, fails
+    assert steps == 3 + GRAPH_STEPS * REPLAYS
 
 
 @pytest.mark.parametrize("chunks", [1, 2, 3])
