@@ -19,7 +19,8 @@ LIB_PATH = os.path.join(LIB_DIR, "libdrcvar_halfspace.so")
 SOURCES = [os.path.join(PKG_DIR, "csrc", "drcvar_halfspace.hip"),
            os.path.join(PKG_DIR, "csrc", "drcvar_mpc.hip"),
            os.path.join(PKG_DIR, "csrc", "drcvar_sampling.hip"),
-           os.path.join(PKG_DIR, "csrc", "drcvar_exchange.hip")]
+           os.path.join(PKG_DIR, "csrc", "drcvar_exchange.hip"),
+           os.path.join(PKG_DIR, "csrc", "drcvar_clearance.hip")]
 INCLUDE_DIR = os.path.join(REPO_DIR, "include")
 HEADERS = [os.path.join(INCLUDE_DIR, h) for h in ("drcvar_halfspace.h", "drcvar_mpc.h",
                                                   "drcvar_sampling.h", "drcvar_exchange.h")]
@@ -96,6 +97,8 @@ EXPORTED_SYMBOLS = (
     "drcvar_mpc_filter_f64_ex",
     "drcvar_sample_trajectories_f64",
     "drcvar_sample_units_f64",
+    "drcvar_min_clearance_f64",
+    "drcvar_min_clearance_f64_ex",
     "drcvar_peer_region_doubles",
     "drcvar_peer_alloc",
     "drcvar_peer_free",
@@ -321,6 +324,12 @@ def _bind(lib):
     lib.drcvar_sample_units_f64.argtypes = [
         ptr, i64, i64, i64, i64, i64, i64, i64, dbl, dbl, dbl, u64, u64, i32, ptr, i64, i64, ptr]
     lib.drcvar_sample_units_f64.restype = ctypes.c_int
+    lib.drcvar_min_clearance_f64.argtypes = [
+        ptr, i64, i64, i64, ptr, i64, i64, i64, i64, i32, dbl, dbl, dbl, dbl, i64, i64, u64, u64, i32,
+        ptr, i64, ptr, ptr]
+    lib.drcvar_min_clearance_f64.restype = ctypes.c_int
+    lib.drcvar_min_clearance_f64_ex.argtypes = lib.drcvar_min_clearance_f64.argtypes[:-1] + [i32, ptr]
+    lib.drcvar_min_clearance_f64_ex.restype = ctypes.c_int
     peerp = ctypes.POINTER(PeerSet)
     lib.drcvar_peer_region_doubles.argtypes = [i64]
     lib.drcvar_peer_region_doubles.restype = i64

@@ -13,6 +13,10 @@
  *                                    of obstacles.
  *   drcvar_sample_units_f64          the same draws for a contiguous block of (obstacle, step)
  *                                    units of a global batch (one rank's shard).
+ *   drcvar_min_clearance_f64[_ex]    Monte Carlo out-of-sample evaluation: many noise realisations
+ *                                    of the obstacles drawn by the same generator and reduced to
+ *                                    each trajectory's minimum clearance (documented at its
+ *                                    declaration below); many-realisation form of main.py:128-138.
  *
  * Random numbers: Philox4x32-10 (counter-based; key = seed, counter = (unit * ceil(N/2) + pair,
  * stream)), one call per PAIR of samples of a unit -> two (32-bit uniform, 32-bit turn) pairs ->
@@ -69,6 +73,62 @@ int drcvar_sample_units_f64(const double* nominal, int64_t n_obstacles, int64_t 
                             int64_t n_samples, double l00, double l10, double l11, uint64_t seed,
                             uint64_t stream_offset, int32_t zero_first_step, double* out,
                             int64_t su, int64_t sn, void* stream);
+
+/*
+ * Monte Carlo out-of-sample collision evaluation (csrc/drcvar_clearance.hip).  The reference checks
+ * its filtered trajectories against ONE Laplace realisation per obstacle (main.py:128-138,
+ * simulation/obstacles.py:79-113, simulation/environment.py:108-140); this entry draws
+ * n_realizations of them on the device and reduces each to the trajectory's minimum clearance
+ * without storing a realisation.
+ *
+ * For realisation m in [m_begin, m_begin + n_realizations), obstacle o, step t, trajectory k:
+ *   one Philox4x32-10 call per (m, o, t): counter (g lo, g hi, stream_offset lo, hi),
+ *   g = m * (O * T) + o * T + t, key = seed (the sampler's convention).  The draw is a pure function
+ *   of (seed, stream_offset, m, o, t, O, T): independent of the launch geometry, of K and of the
+ *   [m_begin, m_begin + M) window that asks for it.  Words x0..x3, E(x) = -log((x + 1/2) 2^-32):
+ *     noise_kind 1 (Laplace, per axis)  n = (p0 (E(x0) - E(x1)), p1 (E(x2) - E(x3))), scales
+ *                  bx = p0, by = p1 >= 0, p2 ignored: the reference's scale * (e1 - e2),
+ *                  a difference of two Exp(1) draws (obstacles.py:106-108), with
+ *                  scale = sqrt(diag(noise_cov) / 2) (:100);
+ *     noise_kind 0 (Gaussian N(0, L L^T), L = [[p0, 0], [p1, p2]])  (x0, x1) -> Box-Muller -> z,
+ *                  n = L z as in the sampler; x2 and x3 are unused.
+ *   zero_first_step nonzero: t = 0 carries no noise and makes no Philox call (obstacles.py:96).
+ *   d2(k, m, o, t) = |ego[k, t] - (nominal[o, t] + n(m, o, t))|^2: all K trajectories see the same
+ *   draws (common random numbers).
+ *
+ * ego            [n_traj, n_steps, 2] positions (strides ego_sk, ego_st; coords adjacent)
+ * nominal        [n_obstacles, n_steps, 2] (strides nom_so, nom_st; coords adjacent)
+ * combined_radius  R = robot radius + obstacle radius
+ * min_clearance  [n_traj, n_realizations], row stride out_sk:
+ *                min_clearance[k, m - m_begin] = sqrt(min over (o, t) of d2) - R
+ *                (one correctly rounded sqrt, taken at the end)
+ * step_hits      [n_traj, n_steps] contiguous, or NULL: step_hits[k, t] = #{m : min over o of
+ *                d2 < R * R} (R * R rounded once on the host).  The call SETS it.
+ * step_splits    (_ex) workgroup rows the step range is split over; 0 = chosen from the sizes.  The
+ *                result does not depend on it, bit for bit.
+ *
+ * 1 <= n_traj <= 8, n_obstacles * n_steps <= 2^20, m_begin + n_realizations <= 2^40 (and at most
+ * 2^39 realisations per call), otherwise DRCVAR_ERR_UNSUPPORTED.  A null pointer, a negative size,
+ * a NaN parameter, a negative Laplace scale or a negative radius: DRCVAR_ERR_INVALID_ARGUMENT.
+ * n_realizations == 0: DRCVAR_OK, no kernel launched.  n_obstacles * n_steps == 0 with
+ * n_realizations > 0: min_clearance is filled with +inf.  Non-finite positions give unspecified
+ * clearances, never an out-of-range access (no index depends on data).
+ */
+int drcvar_min_clearance_f64(const double* ego, int64_t n_traj, int64_t ego_sk, int64_t ego_st,
+                             const double* nominal, int64_t n_obstacles, int64_t n_steps,
+                             int64_t nom_so, int64_t nom_st, int32_t noise_kind, double p0,
+                             double p1, double p2, double combined_radius, int64_t m_begin,
+                             int64_t n_realizations, uint64_t seed, uint64_t stream_offset,
+                             int32_t zero_first_step, double* min_clearance, int64_t out_sk,
+                             int64_t* step_hits, void* stream);
+
+int drcvar_min_clearance_f64_ex(const double* ego, int64_t n_traj, int64_t ego_sk, int64_t ego_st,
+                                const double* nominal, int64_t n_obstacles, int64_t n_steps,
+                                int64_t nom_so, int64_t nom_st, int32_t noise_kind, double p0,
+                                double p1, double p2, double combined_radius, int64_t m_begin,
+                                int64_t n_realizations, uint64_t seed, uint64_t stream_offset,
+                                int32_t zero_first_step, double* min_clearance, int64_t out_sk,
+                                int64_t* step_hits, int32_t step_splits, void* stream);
 
 #ifdef __cplusplus
 }
