@@ -20,7 +20,8 @@ SOURCES = [os.path.join(PKG_DIR, "csrc", "drcvar_halfspace.hip"),
            os.path.join(PKG_DIR, "csrc", "drcvar_mpc.hip"),
            os.path.join(PKG_DIR, "csrc", "drcvar_sampling.hip"),
            os.path.join(PKG_DIR, "csrc", "drcvar_exchange.hip"),
-           os.path.join(PKG_DIR, "csrc", "drcvar_clearance.hip")]
+           os.path.join(PKG_DIR, "csrc", "drcvar_clearance.hip"),
+           os.path.join(PKG_DIR, "csrc", "drcvar_sampled.hip")]
 INCLUDE_DIR = os.path.join(REPO_DIR, "include")
 HEADERS = [os.path.join(INCLUDE_DIR, h) for h in ("drcvar_halfspace.h", "drcvar_mpc.h",
                                                   "drcvar_sampling.h", "drcvar_exchange.h")]
@@ -99,6 +100,8 @@ EXPORTED_SYMBOLS = (
     "drcvar_sample_units_f64",
     "drcvar_min_clearance_f64",
     "drcvar_min_clearance_f64_ex",
+    "drcvar_sampled_halfspaces_f64",
+    "drcvar_sampled_launch_plan",
     "drcvar_peer_region_doubles",
     "drcvar_peer_alloc",
     "drcvar_peer_free",
@@ -330,6 +333,12 @@ def _bind(lib):
     lib.drcvar_min_clearance_f64.restype = ctypes.c_int
     lib.drcvar_min_clearance_f64_ex.argtypes = lib.drcvar_min_clearance_f64.argtypes[:-1] + [i32, ptr]
     lib.drcvar_min_clearance_f64_ex.restype = ctypes.c_int
+    lib.drcvar_sampled_halfspaces_f64.argtypes = [
+        ptr, i64, i64, i64, i64, i64, i64, i64, dbl, dbl, dbl, u64, u64, i32, ptr, i64,
+        dbl, dbl, dbl, dbl, dbl, ptr, ptr, ptr, i64, i64, ptr]
+    lib.drcvar_sampled_halfspaces_f64.restype = ctypes.c_int
+    lib.drcvar_sampled_launch_plan.argtypes = [i64, i32p, i32p]
+    lib.drcvar_sampled_launch_plan.restype = ctypes.c_int
     peerp = ctypes.POINTER(PeerSet)
     lib.drcvar_peer_region_doubles.argtypes = [i64]
     lib.drcvar_peer_region_doubles.restype = i64
@@ -389,3 +398,11 @@ def launch_plan(n_samples: int):
     b, p, nb = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
     check(lib().drcvar_launch_plan(int(n_samples), ctypes.byref(b), ctypes.byref(p), ctypes.byref(nb)))
     return b.value, p.value, nb.value
+
+
+def sampled_launch_plan(n_samples: int):
+    """(threads_per_unit, pairs_per_thread) of the sampled-halfspace kernel for ``n_samples``
+    (host-only query); a plan holds ``2 * threads * pairs`` samples."""
+    b, p = ctypes.c_int32(), ctypes.c_int32()
+    check(lib().drcvar_sampled_launch_plan(int(n_samples), ctypes.byref(b), ctypes.byref(p)))
+    return b.value, p.value

@@ -7,8 +7,11 @@ These are the batched calls everything else is built on:
   horizon loop of ``simulation/environment.py:82-104``).
 * :func:`offsets_given_h`   — ``drcvar_offsets_given_h_f64``: ``cvar_halfspace`` /
   ``dr_cvar_halfspace`` for caller-supplied directions (``core/risk_metrics.py:267-338``).
+* :func:`sampled_halfspaces` — ``drcvar_sampled_halfspaces_f64``: the same records straight from
+  the nominal paths ``[O, T, 2]``, each unit's samples drawn inside the kernel and never stored
+  (``simulation/obstacles.py:43-77`` + ``core/halfspaces.py:196-248`` in one launch).
 
-Both enqueue one kernel on the current HIP stream and return without synchronising.  Inputs must
+All enqueue one kernel on the current HIP stream and return without synchronising.  Inputs must
 be float64 CUDA tensors whose two coordinates are adjacent (last stride 1); any other strides are
 passed to the kernel as they are (no hidden copies).  :class:`PreparedLaunch` freezes the argument
 tuple of a repeated call (bench loops, graph capture) so the per-launch host cost is one ctypes
@@ -168,6 +171,119 @@ def safe_halfspaces(samples: torch.Tensor, ego: torch.Tensor, params: RiskParams
     """
     launch, out = prepare_safe_halfspaces(samples, ego, params, out, stream, status=status)
     if samples.shape[0] * samples.shape[1] > 0:
+        launch()
+    return out
+
+
+DEFAULT_NOISE_COV = ((0.01, 0.0), (0.0, 0.01))  # the reference's default, simulation/obstacles.py:134
+
+
+def _noise_factor(noise_cov, chol):
+    """(l00, l10, l11): ``chol`` as given (it may be singular or zero), else the lower Cholesky
+    factor of ``noise_cov`` exactly as ``sample_trajectories_device`` forms it."""
+    if chol is not None:
+        l00, l10, l11 = (float(v) for v in chol)
+        return l00, l10, l11
+    import numpy as np
+    L = np.linalg.cholesky(np.asarray(noise_cov, dtype=np.float64).reshape(2, 2))
+    return float(L[0, 0]), float(L[1, 0]), float(L[1, 1])
+
+
+def prepare_sampled_halfspaces(nominal: torch.Tensor, ego: torch.Tensor, n_samples: int,
+                               params: RiskParams = RiskParams(), noise_cov=DEFAULT_NOISE_COV,
+                               seed: int = 0, stream_offset: int = 0, zero_first_step: bool = True,
+                               unit_begin: int = 0, unit_count: int | None = None,
+                               out: torch.Tensor | None = None, status: torch.Tensor | None = None,
+                               samples_out: torch.Tensor | None = None, stream=None,
+                               chol=None) -> tuple[PreparedLaunch, torch.Tensor]:
+    """Freeze one ``drcvar_sampled_halfspaces_f64`` call: halfspaces straight from the nominal
+    paths, the samples drawn in the kernel and never stored.
+
+    nominal ``[O, T, 2]`` and ego ``[T, 2]`` float64 device tensors with adjacent coordinates;
+    ``1 <= n_samples <= _native.MAX_SAMPLES``.  The noise is ``noise_cov`` through
+    ``np.linalg.cholesky`` (as ``sample_trajectories_device``), or an explicit lower factor
+    ``chol=(l00, l10, l11)``, which may be singular or zero.  With ``unit_count=None`` the whole
+    grid is evaluated and ``out`` is ``[O, T, 8]``; a unit window ``[unit_begin, unit_begin +
+    unit_count)`` (unit ``u = o * T + t``) gives ``[unit_count, 8]``.  ``status`` (int32, one
+    element per unit) receives the ``_native.UNIT_*`` bits; ``samples_out`` (``[units, N, 2]``
+    float64 view with adjacent coordinates; ``[O, T, N, 2]`` contiguous in its first two axes for
+    the whole grid) also receives the samples drawn — the records are the same bits without it.
+    A frozen launch replays the same draw (graph capture included)."""
+    params.validate()
+    if not isinstance(nominal, torch.Tensor) or nominal.device.type != "cuda":
+        raise ValueError("nominal must live on the GPU (HIP device tensor); the engine has no CPU path")
+    if nominal.dtype != torch.float64 or nominal.dim() != 3 or nominal.shape[2] != 2 or \
+            nominal.stride(2) != 1:
+        raise ValueError("nominal must be float64 [O, T, 2] with adjacent coordinates")
+    dev = nominal.device
+    O, T, _ = nominal.shape
+    n = int(n_samples)
+    if n < 1 or n > _native.MAX_SAMPLES:
+        raise ValueError(f"n_samples={n} outside 1..{_native.MAX_SAMPLES} (the sampled form holds a "
+                         "unit on chip; larger units go through the sampler and safe_halfspaces)")
+    _check_pairs(ego, "ego", T, dev)
+    whole = unit_count is None
+    u0 = int(unit_begin)
+    count = O * T - u0 if whole else int(unit_count)
+    if u0 < 0 or count < 0 or u0 + count > O * T:
+        raise ValueError(f"unit range [{u0}, {u0 + count}) outside the {O} x {T} grid")
+    whole = whole and u0 == 0
+    shape = (O, T, OUT_WIDTH) if whole else (count, OUT_WIDTH)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=dev)
+    else:
+        _check_out(out, shape, dev, "[O, T, 8]" if whole else "[units, 8]")
+    if status is not None:
+        _check_status(status, count, dev)
+    su = sn = 0
+    if samples_out is not None:
+        s = samples_out
+        if not isinstance(s, torch.Tensor) or s.dtype != torch.float64 or s.device != dev or \
+                s.shape[-1] != 2 or s.stride(-1) != 1:
+            raise ValueError("samples_out must be a float64 device view with adjacent coordinates")
+        if whole and tuple(s.shape) == (O, T, n, 2) and (O <= 1 or s.stride(0) == T * s.stride(1)):
+            su, sn = s.stride(1), s.stride(2)
+        elif tuple(s.shape) == (count, n, 2):
+            su, sn = s.stride(0), s.stride(1)
+        else:
+            raise ValueError(f"samples_out must have shape {(count, n, 2)}"
+                             f"{' or ' + str((O, T, n, 2)) if whole else ''}, got {tuple(s.shape)}")
+        if sn < 2 or su < n * sn:
+            raise ValueError("samples_out: overlapping samples or units")
+    l00, l10, l11 = _noise_factor(noise_cov, chol)
+    mask = 2 ** 64 - 1
+    args = (ctypes.c_void_p(nominal.data_ptr()), O, T, nominal.stride(0), nominal.stride(1),
+            u0, count, n, l00, l10, l11,
+            ctypes.c_uint64(int(seed) & mask), ctypes.c_uint64(int(stream_offset) & mask),
+            ctypes.c_int32(1 if zero_first_step else 0),
+            ctypes.c_void_p(ego.data_ptr()), ego.stride(0),
+            params.robot_radius, params.obstacle_radius, params.alpha, params.delta, params.epsilon,
+            ctypes.c_void_p(out.data_ptr()),
+            ctypes.c_void_p(status.data_ptr() if status is not None else None),
+            ctypes.c_void_p(samples_out.data_ptr() if samples_out is not None else None), su, sn,
+            ctypes.c_void_p(_stream_handle(dev, stream)))
+    launch = PreparedLaunch(_native.lib().drcvar_sampled_halfspaces_f64, args,
+                            (nominal, ego, out, status, samples_out))
+    return launch, out
+
+
+def sampled_halfspaces(nominal: torch.Tensor, ego: torch.Tensor, n_samples: int,
+                       params: RiskParams = RiskParams(), **kwargs) -> torch.Tensor:
+    """Mean / CVaR / DR-CVaR halfspaces of every (obstacle, step) unit from the NOMINAL paths: one
+    launch draws each unit's ``n_samples`` Gaussian samples in registers and reduces them to the
+    unit's record; no ``[O, T, N, 2]`` buffer exists (arguments: :func:`prepare_sampled_halfspaces`).
+
+    The draw is bit for bit ``sample_trajectories_device`` / ``sample_units_device`` for the same
+    seed and stream offset, and the record agrees with ``safe_halfspaces`` on that draw to
+    rounding (a summation order of its own).  Measured against sampler + ``safe_halfspaces`` on
+    one stream (profiles/sampled/sampled_times.json): C3 (10 x 20 x 1000) 6.4 us
+    against 16.5 us, C4 (64 x 30 x 5000) 59.7 us against 77.6 us; C5 (256 x 50 x 10000) is NOT
+    faster, 0.781 ms against 0.722 ms — above 8192 samples a unit takes a whole CU's registers, so
+    nothing overlaps its selection — and saves only the 2.05 GB buffer.  Nothing dispatches
+    between the two forms, the caller chooses.
+    """
+    launch, out = prepare_sampled_halfspaces(nominal, ego, n_samples, params, **kwargs)
+    if out.numel() > 0:
         launch()
     return out
 

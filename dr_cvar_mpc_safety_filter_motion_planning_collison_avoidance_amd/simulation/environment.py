@@ -110,6 +110,37 @@ class SafetyFilteringEnvironment:
         risk_metrics.commit_singletons(final)  # only once every launch was accepted
         return HalfspaceBatch(record, setup_time=t1 - t0)
 
+    def compute_halfspace_batch_sampled(self, nominal_trajectories, ego_ref_trajectory, n_samples,
+                                        noise_cov=engine.DEFAULT_NOISE_COV, seed=0):
+        """``compute_halfspace_batch`` from the obstacles' NOMINAL paths: each (obstacle, step)
+        unit's ``n_samples`` Gaussian samples around its nominal point are drawn inside the kernel
+        (``engine.sampled_halfspaces``; step 0 noise-free, as the reference's sampler) and no
+        sample trajectory exists on the host or the device.  ``nominal_trajectories``: ``[O, S+1, 2]``
+        (array, list of per-obstacle arrays or device tensor).  Returns the same record
+        (HalfspaceBatch, ``[O, T, 8]``, T = min(len(ref), H)), ready for the device MPC filter.
+        Evaluated with this environment's own parameters (no optimiser-singleton carry-over: the
+        reference has no such call to mirror)."""
+        n_steps = min(len(ego_ref_trajectory), self.HORIZON)               # environment.py:72
+        self.params.validate()
+        t0 = time.time()
+        dev = risk_metrics.device()
+        if isinstance(nominal_trajectories, torch.Tensor):
+            nom_d = nominal_trajectories.to(dev, torch.float64)[:, :n_steps]
+        else:
+            nom = np.asarray(nominal_trajectories, dtype=np.float64)
+            nom_d = torch.as_tensor(np.ascontiguousarray(nom.reshape(len(nom), -1, 2)[:, :n_steps])).to(dev)
+        if nom_d.shape[1] < n_steps:
+            raise ValueError(f"nominal trajectories have {nom_d.shape[1]} steps, the horizon needs {n_steps}")
+        ego = np.asarray(ego_ref_trajectory, dtype=np.float64)[:n_steps] @ self.C.T  # :92
+        ego_d = torch.as_tensor(np.ascontiguousarray(ego).reshape(n_steps, 2)).to(dev)
+        if nom_d.shape[0] == 0 or n_steps == 0:
+            return HalfspaceBatch(torch.empty((nom_d.shape[0], n_steps, engine.OUT_WIDTH),
+                                              dtype=torch.float64, device=dev))
+        t1 = time.time()
+        record = engine.sampled_halfspaces(nom_d, ego_d, n_samples, self.params,
+                                           noise_cov=noise_cov, seed=seed)
+        return HalfspaceBatch(record, setup_time=t1 - t0)
+
     def _pinned_stage(self, n_doubles):
         """The cached pinned host buffer the trajectories are staged through (one allocation for
         the environment's lifetime unless a larger batch arrives).  Before it is refilled, the

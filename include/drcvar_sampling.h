@@ -130,6 +130,55 @@ int drcvar_min_clearance_f64_ex(const double* ego, int64_t n_traj, int64_t ego_s
                                 int32_t zero_first_step, double* min_clearance, int64_t out_sk,
                                 int64_t* step_hits, int32_t step_splits, void* stream);
 
+/*
+ * Safe halfspaces straight from the nominal paths (csrc/drcvar_sampled.hip): replaces
+ * generate_obstacle_sample_trajectories (simulation/obstacles.py:43-77) followed by
+ * compute_safe_halfspaces (core/halfspaces.py:196-248) over the horizon loop
+ * (simulation/environment.py:82-104) — on the device, drcvar_sample_units_f64 followed by
+ * drcvar_safe_halfspaces_f64_v2 — by ONE launch that draws each unit's samples into registers,
+ * reduces them to the unit's record and stores nothing else.  No sample buffer is allocated.
+ *
+ * Units [unit_begin, unit_begin + unit_count) of the global [n_obstacles, n_steps] grid, unit
+ * u = o * n_steps + t.  The samples of unit u are bit for bit those drcvar_sample_units_f64 writes
+ * for the same (nominal, n_samples, L, seed, stream_offset, zero_first_step): same Philox counter,
+ * same pairing, same arithmetic.  The record is that of drcvar_safe_halfspaces_f64_v2 on those
+ * samples: the same mathematics (fp64 mean, separating direction, exact order statistic of rank
+ * min(floor(alpha N), N - 1), L = tau + dsum / k, the same sentinels and status bits), summed in
+ * this kernel's own fixed order, so the two agree to rounding, and each is bitwise reproducible.
+ *
+ * nominal      [n_obstacles, n_steps, 2] GLOBAL nominal path (strides nom_so, nom_st; coords adjacent)
+ * ego          [n_steps, 2] (row stride ego_stride; coords adjacent): the unit's step picks the row
+ * out          [unit_count, DRCVAR_OUT_WIDTH] contiguous records, DRCVAR_COL_*
+ * status       [unit_count] DRCVAR_UNIT_* bits, or NULL
+ * samples_out  NULL, or the kernel also stores the samples it drew: unit u at
+ *              samples_out + (u - unit_begin) * su, sample i at + i * sn, coordinates adjacent.
+ *              The records are the same bits with and without it.
+ *
+ * 1 <= n_samples <= DRCVAR_MAX_SAMPLES.  Checked on the host before any launch: a null nominal, ego
+ * or out, a negative size, a unit range outside the grid, a NaN factor or a parameter
+ * drcvar_safe_halfspaces_f64 rejects: DRCVAR_ERR_INVALID_ARGUMENT; n_samples > DRCVAR_MAX_SAMPLES,
+ * a grid beyond the sampler's limits (2^40) or more than 2^31 - 1 units in one call:
+ * DRCVAR_ERR_UNSUPPORTED; unit_count == 0 or n_samples == 0: DRCVAR_OK, nothing launched.
+ * Unit-level exits (sentinels + status) as in drcvar_safe_halfspaces_f64_v2: alpha N > N,
+ * epsilon < 0, a non-finite sum (here from a non-finite nominal position or factor).
+ * Asynchronous on `stream`, no allocation, no synchronisation: the call can be captured in a graph
+ * (a captured launch replays the same draw).
+ */
+int drcvar_sampled_halfspaces_f64(
+    const double* nominal, int64_t n_obstacles, int64_t n_steps, int64_t nom_so, int64_t nom_st,
+    int64_t unit_begin, int64_t unit_count, int64_t n_samples,
+    double l00, double l10, double l11, uint64_t seed, uint64_t stream_offset,
+    int32_t zero_first_step,
+    const double* ego, int64_t ego_stride,
+    double robot_radius, double obstacle_radius, double alpha, double delta, double epsilon,
+    double* out, int32_t* status,
+    double* samples_out, int64_t su, int64_t sn,
+    void* stream);
+
+/* host only: the plan a sample count runs on (threads per unit, Philox pairs per thread; a plan
+ * holds 2 * threads * pairs samples); DRCVAR_ERR_UNSUPPORTED above DRCVAR_MAX_SAMPLES */
+int drcvar_sampled_launch_plan(int64_t n_samples, int32_t* threads, int32_t* pairs_per_thread);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,113 @@
+"""Times the sampled-halfspace kernel (drcvar_sampled_halfspaces_f64: halfspaces straight from the
+nominal paths, samples drawn in-kernel and never stored) against the two-launch path it replaces,
+and writes profiles/sampled/sampled_times.json.
+
+    python scripts/micro/sampled_times.py [--out FILE]
+
+Shapes: C3 (10 x 20 x 1000), C4 (64 x 30 x 5000), C5 (256 x 50 x 10000).  Every figure is
+device-event time over `--launches` back-to-back launches after a warm-up, repeated `--repeats`
+times: the median and the spread (min, max) are reported, in ms per launch.
+
+  baseline         sample_trajectories_device followed by safe_halfspaces on one stream
+  sampler_alone    the first half of it, halfspace_alone the second (on the stored draw)
+  sampled          the one-launch form, samples_out NULL
+  sampled_keep     the same with samples_out: it also stores the draw
+  bytes_not_allocated   the [O, T, N, 2] fp64 buffer the sampled form does without
+  max_abs_diff     sampled records against the two-launch records on the same draw
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
+sys.path.insert(0, REPO)
+
+from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd import _native, engine, synthetic  # noqa: E402
+from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd.engine import RiskParams  # noqa: E402
+from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd.simulation import obstacles  # noqa: E402
+
+SHAPES = [("C3", 10, 20, 1000), ("C4", 64, 30, 5000), ("C5", 256, 50, 10000)]
+SEED = 5
+
+
+def timed(fn, launches, repeats, warmup=3):
+    """ms per launch: (median, min, max) over `repeats` windows of `launches` launches."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(launches):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b) / launches)
+    return {"ms": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms))}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "sampled", "sampled_times.json"))
+    ap.add_argument("--launches", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=5)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("sampled_times.py measures on the GPU; there is none")
+    dev = torch.device("cuda", 0)
+    params = RiskParams()
+    result = {"device": torch.cuda.get_device_name(0), "launches": args.launches, "repeats": args.repeats,
+              "kernel_source_key": _native.source_key("drcvar_sampled.hip"),
+              "halfspace_source_key": _native.source_key(),
+              "timing": "device events around `launches` back-to-back launches, ms per launch: "
+                        "median (min, max) over `repeats` windows", "shapes": []}
+    for name, O, T, N in SHAPES:
+        rng = np.random.default_rng(O * 1000 + T)
+        nominal = torch.from_numpy(rng.uniform(-5.0, 5.0, size=(O, T, 2))).to(dev)
+        ego = synthetic.straight_line_ego(T, dev, start=(-7.0, -6.0), goal=(-5.5, -5.5))
+        samples = torch.empty((O, T, N, 2), dtype=torch.float64, device=dev)
+        two = torch.empty((O, T, 8), dtype=torch.float64, device=dev)
+        one = torch.empty((O, T, 8), dtype=torch.float64, device=dev)
+        hs, _ = engine.prepare_safe_halfspaces(samples, ego, params, out=two)
+        sampled, _ = engine.prepare_sampled_halfspaces(nominal, ego, N, params, seed=SEED, out=one)
+        keep, _ = engine.prepare_sampled_halfspaces(nominal, ego, N, params, seed=SEED, out=one,
+                                                    samples_out=samples)
+
+        def draw():
+            obstacles.sample_trajectories_device(nominal, N, seed=SEED, out=samples)
+
+        def baseline():
+            draw()
+            hs()
+
+        row = {"shape": name, "O": O, "T": T, "N": N, "plan": _native.sampled_launch_plan(N),
+               "bytes_not_allocated": O * T * N * 16}
+        row["baseline_sampler_then_halfspaces"] = timed(baseline, args.launches, args.repeats)
+        row["sampler_alone"] = timed(draw, args.launches, args.repeats)
+        row["halfspace_alone"] = timed(hs, args.launches, args.repeats)
+        row["sampled"] = timed(sampled, args.launches, args.repeats)
+        baseline()
+        sampled()
+        torch.cuda.synchronize()
+        row["max_abs_diff_vs_two_launch"] = float((one - two).abs().max())
+        row["sampled_keep_samples"] = timed(keep, args.launches, args.repeats)
+        row["ratio_sampled_to_baseline"] = row["sampled"]["ms"] / row["baseline_sampler_then_halfspaces"]["ms"]
+        row["sampled_faster_beyond_spread"] = bool(
+            row["sampled"]["ms_max"] < row["baseline_sampler_then_halfspaces"]["ms_min"])
+        result["shapes"].append(row)
+        print(json.dumps(row), flush=True)
+        del samples
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
