@@ -56,26 +56,6 @@ struct ClearArgs {
   int64_t steps_per_split;
 };
 
-// LogScale for lam (see drcvar_generator.inc), as the sampler makes it.
-LogScale make_log_scale(double lam) {
-  LogScale c{};
-  c.lam = lam;
-  c.q0 = lam * (1.0 / 192.0);
-  c.q1 = lam * (1.0 / 80.0);
-  c.q2 = lam * (1.0 / 32.0);
-  c.q3 = lam * (1.0 / 12.0);
-  c.q4 = lam * 0.25;
-  const long double e2 = -2.0L * static_cast<long double>(lam) * 0.693147180559945309417232121458176568L;
-  double eh = static_cast<double>(e2);
-  uint64_t bits;
-  std::memcpy(&bits, &eh, sizeof bits);
-  bits &= ~uint64_t{0x7f};  // 53 - 7 = 46 significant bits
-  std::memcpy(&eh, &bits, sizeof bits);
-  c.eh = eh;
-  c.el = static_cast<double>(e2 - static_cast<long double>(eh));
-  return c;
-}
-
 // The noise of one (m, o, t) from its Philox call.  kLaplace: the log carries lam = 1/2, so
 // scaled_neg2_log_u32 is E = -log u; otherwise lam = 1 and (x0, x1) are Box-Muller's radius and
 // angle words (x2, x3 unused).

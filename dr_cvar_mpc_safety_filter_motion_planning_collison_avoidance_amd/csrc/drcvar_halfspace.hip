@@ -37,9 +37,6 @@
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kCap = 128;          // candidates ranked directly (per-wave region size in LDS)
-constexpr int kMaxValueIters = 3;  // value-linear refinements before switching to integer keys
 constexpr double kSentinel = 100.0;
 // sample load forms (kernel template)
 constexpr int kLoadPair = 0, kLoadVec = 1, kLoadNt = 2;
@@ -83,105 +80,8 @@ __device__ unsigned long long g_stamps[kStampUnits * kStamps];
   } while (0)
 #endif
 
-// Launch-uniform scalars, precomputed on the host so the per-unit critical path carries as few
-// fp64 divisions as possible.
-struct Params {
-  double rc;              // robot_radius + obstacle_radius
-  double alpha;
-  double delta;
-  double epsilon;
-  double eps_over_alpha;  // lambda* epsilon (risk_metrics.py:110,122)
-  double inv_n;           // 1 / N
-  double inv_n0;          // 1 / size of the window's subsample (pilot: min(N, 64); row 0: min(N, threads))
-  double k;               // alpha N
-  double inv_k;           // 1 / (alpha N)
-  double z_alpha;         // standard-normal alpha-quantile: centre of the fast-path window
-  double window_sd;       // half-width of the fast-path window, in sd of d
-  double z_lo;            // z_alpha - window_sd: low edge of the window, in sd of d
-  double hist_scale;      // bins / (2 window_sd): bins per sd of d (set per launch plan)
-  uint32_t rank;          // min(floor(alpha N), N - 1): 0-based rank of tau
-  int unbounded;          // alpha N > N: both LPs unbounded (tau -> -inf), solver-failure sentinel
-  double degenerate_sq;   // smallest x with sqrt(x) >= 1e-10: |v| < 1e-10  <=>  v.v < degenerate_sq
-};
-
-// 1/sqrt(x) to ~1 ulp: hardware seed + one Newton step (the exact sqrt + divide sequence is far
-// longer and sits on the critical path of every unit)
-__device__ __forceinline__ double rsqrt_nr(double x) {
-  const double y = __builtin_amdgcn_rsq(x);
-  return y * fma(-0.5 * x * y, y, 1.5);
-}
-
-// ---------------------------------------------------------------------------------------------
-// wave primitives: DPP row permutations (each an involution, so every lane of a row ends with the
-// bitwise-identical value), then the four row results combined through readlane in fixed order
-// ---------------------------------------------------------------------------------------------
-// (mov_dpp, not update_dpp with an old value of 0: every lane of these permutations has a source,
-// so the old value is never used, and materialising it cost two v_mov plus a DPP hazard wait per
-// stage of every reduction on the chain)
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
-constexpr int kDppQuadXor1 = 0xB1;    // quad_perm [1,0,3,2]
-constexpr int kDppQuadXor2 = 0x4E;    // quad_perm [2,3,0,1]
-constexpr int kDppHalfMirror = 0x141; // row_half_mirror
-constexpr int kDppMirror = 0x140;     // row_mirror
-
-struct OpAdd {
-  __device__ static double f(double a, double b) { return a + b; }
-};
-struct OpMin {
-  __device__ static double f(double a, double b) { return fmin(a, b); }
-};
-struct OpMax {
-  __device__ static double f(double a, double b) { return fmax(a, b); }
-};
-
-// gfx950 lane swaps: permlane16_swap exchanges odd rows of its first operand with even rows of
-// its second, permlane32_swap the upper half of the first with the lower half of the second.
-// With both operands = v, element [0] holds rows (0,0,2,2) / halves (lo,lo) and element [1] rows
-// (1,1,3,3) / halves (hi,hi), so Op([0], [1]) combines row pairs / halves in every lane at once.
-// a wave-uniform value moved to SGPRs (keeps uniform scalars out of the VGPR budget)
-__device__ __forceinline__ double uniform_f64(double v) {
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float uniform_f32(float v) {
-  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
-}
-
-template <class Op>
-__device__ __forceinline__ double swap_combine16(double v) {
-  const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(v), __double2loint(v), false, false);
-  const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(v), __double2hiint(v), false, false);
-  return Op::f(__hiloint2double(hi[0], lo[0]), __hiloint2double(hi[1], lo[1]));
-}
-template <class Op>
-__device__ __forceinline__ double swap_combine32(double v) {
-  const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(v), __double2loint(v), false, false);
-  const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(v), __double2hiint(v), false, false);
-  return Op::f(__hiloint2double(hi[0], lo[0]), __hiloint2double(hi[1], lo[1]));
-}
-
-// Result is uniform across the wave (bitwise: every lane evaluates the same tree,
-// ((r0 + r1) + (r2 + r3)) over the row results).  Requires all 64 lanes active.
-// Measured (scripts/micro/reduce.hip): ~190 cycles latency, ~150 cycles per extra independent value.
-template <class Op>
-__device__ __forceinline__ double wave_reduce(double v) {
-  v = Op::f(v, dpp_f64<kDppQuadXor1>(v));
-  v = Op::f(v, dpp_f64<kDppQuadXor2>(v));
-  v = Op::f(v, dpp_f64<kDppHalfMirror>(v));
-  v = Op::f(v, dpp_f64<kDppMirror>(v));
-  return uniform_f64(swap_combine32<Op>(swap_combine16<Op>(v)));
-}
+// the selection toolkit shared with drcvar_sampled.hip: Params, reductions, histogram scan, ranking
+#include "drcvar_selection.inc"
 
 // fp32 sum over the wave, same tree (the DPP moves fold into v_add_f32_dpp): ~60 cycles per value.
 __device__ __forceinline__ float wave_sum_f32(float v) {
@@ -193,56 +93,6 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
   v = __int_as_float(a[0]) + __int_as_float(a[1]);
   const auto b = __builtin_amdgcn_permlane32_swap(__float_as_int(v), __float_as_int(v), false, false);
   return uniform_f32(__int_as_float(b[0]) + __int_as_float(b[1]));
-}
-
-// Sum of NW per-wave partials p[0..NW) read by every thread (broadcast LDS reads), fixed
-// pairwise tree — cheaper than a second wave reduction for the small NW of the launch plans.
-template <int NW, class T>
-__device__ __forceinline__ T sum_partials(const T* p) {
-  T v[NW];
-#pragma unroll
-  for (int w = 0; w < NW; ++w) v[w] = p[w];
-#pragma unroll
-  for (int stride = 1; stride < NW; stride *= 2)
-#pragma unroll
-    for (int w = 0; w + stride < NW; w += 2 * stride) v[w] = v[w] + v[w + stride];
-  if constexpr (sizeof(T) == 8) {
-    return uniform_f64(v[0]);
-  } else {
-    return uniform_f32(v[0]);
-  }
-}
-
-template <class Op>
-__device__ __forceinline__ double identity_of();
-template <>
-__device__ __forceinline__ double identity_of<OpAdd>() { return 0.0; }
-template <>
-__device__ __forceinline__ double identity_of<OpMin>() { return INFINITY; }
-template <>
-__device__ __forceinline__ double identity_of<OpMax>() { return -INFINITY; }
-
-// Workgroup reduction of K values.  `slot` is LDS scratch of K*NW doubles owned by the call site
-// (never reused by another call without a barrier in between).  The per-wave partials are
-// combined by a second wave reduction (lane w holds wave w's partial), so the order is fixed.
-template <class Op, int NW, int K>
-__device__ __forceinline__ void block_reduce(double (&v)[K], double* slot) {
-#pragma unroll
-  for (int q = 0; q < K; ++q) v[q] = wave_reduce<Op>(v[q]);
-  if constexpr (NW > 1) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int w = threadIdx.x / kWave;
-    if (lane == 0) {
-#pragma unroll
-      for (int q = 0; q < K; ++q) slot[q * NW + w] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-      const double part = lane < NW ? slot[q * NW + lane] : identity_of<Op>();
-      v[q] = wave_reduce<Op>(part);
-    }
-  }
 }
 
 // KD fp64 and KF fp32 wave sums at once: the same trees as wave_reduce / wave_sum_f32 (so the
@@ -331,142 +181,6 @@ __device__ __forceinline__ void block_sum_moments(double* v, float* f, double* s
   if constexpr (PILOT) asm volatile("" ::"v"(pilot_v->x), "v"(pilot_v->y));
 }
 
-// order-preserving map double -> uint64 (total order on non-NaN values)
-__device__ __forceinline__ uint64_t f64_key(double d) {
-  const uint64_t u = static_cast<uint64_t>(__double_as_longlong(d));
-  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-
-// Monotone (non-decreasing) map of the candidate interval [lo, hi] onto NB histogram bins.
-template <int LOG_NB>
-struct BucketMap {
-  static constexpr int NB = 1 << LOG_NB;
-  bool value_mode;
-  double lo, scale;
-  uint64_t klo;
-  int shift;
-
-  // exact range [lo_, hi_] of the candidates, lo_ < hi_: bucket(lo_) = 0 < bucket(hi_)
-  __device__ __forceinline__ void init_range(double lo_, double hi_, int iter) {
-    lo = lo_;
-    const double range = hi_ - lo_;
-    scale = static_cast<double>(NB) / range;
-    value_mode = iter < kMaxValueIters && range > 0.0 && scale < 1e300 && range * scale >= 1.0;
-    klo = f64_key(lo_);
-    const uint64_t diff = f64_key(hi_) - klo;  // >= 1 when hi > lo
-    const int bits = 64 - __builtin_clzll(diff | 1ull);
-    shift = bits > LOG_NB ? bits - LOG_NB : 0;
-  }
-  __device__ __forceinline__ int operator()(double d) const {
-    if (value_mode) {
-      const double t = fmin(fmax((d - lo) * scale, 0.0), static_cast<double>(NB - 1));
-      return static_cast<int>(t);
-    }
-    return static_cast<int>((f64_key(d) - klo) >> shift);  // key mode: lo <= d <= hi only
-  }
-};
-
-struct ScanResult {
-  int bin;
-  uint32_t below, cnt;
-  bool found;  // false when the histogram holds fewer than rr + 1 samples
-};
-
-// Histogram storage: lane l of a scanning wave owns bins [l*B, (l+1)*B), B = NB/64.  One padding
-// word after every B bins makes the owner reads conflict-free (lane stride B+1 words, B+1 odd).
-template <int NB>
-__device__ __forceinline__ int hist_slot(int bin) {  // bin >= 0
-  constexpr unsigned B = NB / kWave;
-  const unsigned b = static_cast<unsigned>(bin);
-  return static_cast<int>(b + b / B);
-}
-template <int NB>
-constexpr int hist_words() {
-  return NB + kWave;
-}
-
-// Inclusive prefix sum over the 64 lanes: DPP row shifts within each row of 16, then the row
-// totals (lanes 15, 31, 47) added through readlane — no LDS round trips.
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x, int lane) {
-  constexpr int kRowShr1 = 0x111, kRowShr2 = 0x112, kRowShr4 = 0x114, kRowShr8 = 0x118;
-  int v = static_cast<int>(x);
-  v += __builtin_amdgcn_update_dpp(0, v, kRowShr1, 0xF, 0xF, true);
-  v += __builtin_amdgcn_update_dpp(0, v, kRowShr2, 0xF, 0xF, true);
-  v += __builtin_amdgcn_update_dpp(0, v, kRowShr4, 0xF, 0xF, true);
-  v += __builtin_amdgcn_update_dpp(0, v, kRowShr8, 0xF, 0xF, true);
-  const int r0 = __builtin_amdgcn_readlane(v, 15);
-  const int r1 = __builtin_amdgcn_readlane(v, 31);
-  const int r2 = __builtin_amdgcn_readlane(v, 47);
-  const int row = lane >> 4;
-  v += (row >= 1 ? r0 : 0) + (row >= 2 ? r1 : 0) + (row >= 3 ? r2 : 0);
-  return static_cast<uint32_t>(v);
-}
-
-// Any wave: the bin holding the sample of rank rr (0-based) and the counts below / inside it.
-// Result is uniform across the wave.
-template <int NB>
-__device__ __forceinline__ void load_bins(const uint32_t* hist, int lane, uint32_t (&h)[NB / kWave]) {
-  constexpr int B = NB / kWave;
-  const uint32_t* mine = hist + lane * (B + 1);
-#pragma unroll
-  for (int q = 0; q < B; ++q) h[q] = mine[q];
-}
-
-// Same, with this lane's bins already loaded (load_bins) — lets the caller issue the histogram
-// reads together with its other post-barrier LDS reads.
-template <int NB>
-__device__ __forceinline__ ScanResult scan_loaded_bins(const uint32_t (&h)[NB / kWave], uint32_t rr,
-                                                      int lane) {
-  constexpr int B = NB / kWave;  // contiguous bins per lane
-  uint32_t s = 0;
-#pragma unroll
-  for (int q = 0; q < B; ++q) s += h[q];
-  const uint32_t incl = wave_inclusive_scan(s, lane);
-  const unsigned long long hit = __ballot(incl > rr);
-  if (hit == 0ull) return ScanResult{0, 0u, 0u, false};
-  const int owner = __ffsll(static_cast<long long>(hit)) - 1;  // uniform
-  // in the owner lane: first bin whose running count passes rr (branch-free over the B bins)
-  uint32_t cum = incl - s;
-  int bin = lane * B + B - 1;
-  uint32_t below = 0, cnt = 0;
-  bool done = false;
-#pragma unroll
-  for (int q = 0; q < B; ++q) {
-    const bool take = !done && cum + h[q] > rr;
-    bin = take ? lane * B + q : bin;
-    below = take ? cum : below;
-    cnt = take ? h[q] : cnt;
-    done = done || take;
-    cum += h[q];
-  }
-  return ScanResult{__builtin_amdgcn_readlane(bin, owner),
-                    static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(below), owner)),
-                    static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cnt), owner)),
-                    true};
-}
-
-template <int NB>
-__device__ __forceinline__ ScanResult scan_bins(const uint32_t* hist, uint32_t rr, int lane) {
-  uint32_t h[NB / kWave];
-  load_bins<NB>(hist, lane, h);
-  return scan_loaded_bins<NB>(h, rr, lane);
-}
-
-__device__ __forceinline__ bool in_range(double d, double lo, double hi) {
-  return lo <= d && d <= hi;  // false for the NaN padding of idle slots
-}
-
-// MeanSafeHalfspace (core/halfspaces.py:84-94): direction from the ORIGIN, offset
-// -(h.mu - R_c |h|), with compute_separating_vector's [1, 0] fallback
-__device__ __forceinline__ void mean_halfspace(double mux, double muy, double rc, double* m0,
-                                               double* m1, double* g) {
-  const double nm = sqrt(mux * mux + muy * muy);
-  const bool degenerate = nm < 1e-10;
-  *m0 = degenerate ? 1.0 : mux / nm;
-  *m1 = degenerate ? 0.0 : muy / nm;
-  *g = -((*m0 * mux + *m1 * muy) - rc * sqrt(*m0 * *m0 + *m1 * *m1));
-}
-
 // columns 0..2 of the record (the mean halfspace), by one lane
 __device__ __forceinline__ void write_mean_halfspace(double* rec, double mux, double muy,
                                                      double rc, int lane) {
@@ -528,12 +242,6 @@ __device__ __forceinline__ void peer_store_record(const PeerArgs& pa, unsigned l
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// d_i = h . xi_i — one expression, used both for the register-resident samples and for re-reads,
-// so both paths see bitwise-identical values (core/risk_metrics.py:145,233: h @ samples.T)
-__device__ __forceinline__ double project(double h0, double h1, double x, double y) {
-  return fma(h0, x, h1 * y);
-}
-
 template <bool VEC>
 __device__ __forceinline__ double project_at(const double* base, int i, int64_t s_samp, double h0,
                                              double h1) {
@@ -546,25 +254,9 @@ __device__ __forceinline__ double project_at(const double* base, int i, int64_t 
   }
 }
 
-// Value-linear position in the fast-path window: t(d) = d * scale + off (one fma, rounded once,
-// so monotone non-decreasing in d for any scale > 0).  Below the window: t < 0; inside: 0 <= t <
-// NB (bin = trunc(t) <= NB - 1); above it (and the +inf padding): t >= NB.
-struct LinearMap {
-  double scale, off;
-  __device__ __forceinline__ double operator()(double d) const { return fma(d, scale, off); }
-};
-
 // LDS accesses of one wave complete in order; this keeps the compiler from moving them across a
 // wave-local hand-off (no barrier needed within a wave)
 __device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
-
-// Per-wave ordered compaction step: append the candidates of one row to this wave's LDS region.
-__device__ __forceinline__ void append_candidate(double* region, uint32_t& wbase, bool is_cand,
-                                                 double v, unsigned long long lt_mask) {
-  const unsigned long long ballot = __ballot(is_cand);
-  if (is_cand) region[wbase + __popcll(ballot & lt_mask)] = v;
-  wbase += static_cast<uint32_t>(__popcll(ballot));
-}
 
 // Lane w < NW: the candidate count of wave w (0 elsewhere) — the ranking's input, read by the
 // caller so that it can be issued together with other LDS reads.
@@ -575,78 +267,6 @@ __device__ __forceinline__ uint32_t wave_counts(const uint32_t* wcount, int lane
 // Makes a loaded value available at this point (an empty asm that consumes it): keeps the compiler
 // from sinking independent LDS loads past a branch or a wait, so they share one round trip.
 __device__ __forceinline__ void lds_values_ready(uint32_t v) { asm volatile("" ::"v"(v)); }
-
-// Wave 0 (all lanes active): tau = the candidate of rank rr among the c <= kCap candidates held in
-// per-wave regions cand[w * kCap + i], i < wcount[w] (global order: wave, then position — fixed).
-// Candidates are pulled into registers (g = lane, lane + 64) and compared through readlane, so
-// the O(c^2) ranking never waits on LDS.  Also returns s_cand = sum over candidates below tau of
-// (cand - tau), accumulated in candidate order.  Q = candidate registers per lane: 1 when
-// c <= 64 (the usual case), 2 up to kCap.
-template <int NW, int Q>
-__device__ __forceinline__ double rank_candidates_q(const double* cand, uint32_t cw, uint32_t c,
-                                                    uint32_t rr, int lane, double* s_cand) {
-  int slot[2] = {-1, -1};
-  uint32_t acc = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    const uint32_t nw = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cw), w));
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      const uint32_t g = lane + q * kWave;
-      if (g >= acc && g < acc + nw) slot[q] = w * kCap + static_cast<int>(g - acc);
-    }
-    acc += nw;
-  }
-  double mine[2] = {NAN, NAN};  // candidates g = lane, lane + 64
-#pragma unroll
-  for (int q = 0; q < Q; ++q)
-    if (slot[q] >= 0) mine[q] = cand[slot[q]];
-  // per candidate v (lane-parallel): #{z < v}, #{z == v} and sum_{z < v} (z - v); the lane of
-  // tau then holds s_cand itself, so no reduction follows the ranking
-  uint32_t less[2] = {0u, 0u}, eq[2] = {0u, 0u};
-  double sl[2] = {0.0, 0.0};
-  const uint32_t c0 = c < kWave ? c : kWave;
-  for (uint32_t i = 0; i < c0; ++i) {  // uniform trip count
-    const double z = readlane_f64(mine[0], static_cast<int>(i));
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      const bool lt = z < mine[q];
-      less[q] += lt ? 1u : 0u;
-      eq[q] += (z == mine[q]) ? 1u : 0u;
-      sl[q] += lt ? z - mine[q] : 0.0;
-    }
-  }
-  for (uint32_t i = kWave; Q == 2 && i < c; ++i) {
-    const double z = readlane_f64(mine[1], static_cast<int>(i - kWave));
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      const bool lt = z < mine[q];
-      less[q] += lt ? 1u : 0u;
-      eq[q] += (z == mine[q]) ? 1u : 0u;
-      sl[q] += lt ? z - mine[q] : 0.0;
-    }
-  }
-  bool found = false;
-  double found_v = 0.0, found_s = 0.0;
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    if (lane + q * kWave < c && less[q] <= rr && rr < less[q] + eq[q]) {
-      found = true;
-      found_v = mine[q];
-      found_s = sl[q];
-    }
-  }
-  const unsigned long long fb = __ballot(found);
-  const int src = __ffsll(static_cast<long long>(fb)) - 1;
-  *s_cand = readlane_f64(found_s, src);
-  return readlane_f64(found_v, src);
-}
-template <int NW>
-__device__ __forceinline__ double rank_candidates(const double* cand, uint32_t cw, uint32_t c,
-                                                  uint32_t rr, int lane, double* s_cand) {
-  return c <= static_cast<uint32_t>(kWave) ? rank_candidates_q<NW, 1>(cand, cw, c, rr, lane, s_cand)
-                                           : rank_candidates_q<NW, 2>(cand, cw, c, rr, lane, s_cand);
-}
 
 // Exact selection for the units the register fast path does not finish (degenerate moments, or a
 // first-pass bucket with more than kCap samples).  It re-reads the unit's samples (L2/MALL-hot)
@@ -747,38 +367,6 @@ __device__ __forceinline__ void select_from_memory(const Proj& proj, int n, doub
   const double n_below = static_cast<double>(rank - rr);
   *tau_out = tau;
   *dsum_out = (s_below - n_below * (tau - mu_d)) + s_cand;
-}
-
-// compute_separating_vector(ego, mu) (core/geometry.py:35-53): (mu - ego) / |mu - ego|, [1, 0]
-// below 1e-10 (rsqrt + one Newton step).  Branch-free: an overflowing norm (n2 = inf) selects
-// 1/inf = 0, as diff / norm gives 0 (finite diff) or NaN (infinite diff); a NaN n2 stays NaN.
-__device__ __forceinline__ void separating_direction(double mux, double muy, double e0, double e1,
-                                                     double deg_sq, double* h0, double* h1) {
-  const double dx = mux - e0, dy = muy - e1;
-  const double n2 = dx * dx + dy * dy;
-  const double inv = n2 == INFINITY ? 0.0 : rsqrt_nr(n2);
-  const bool degenerate = n2 < deg_sq;
-  *h0 = degenerate ? 1.0 : dx * inv;
-  *h1 = degenerate ? 0.0 : dy * inv;
-}
-
-// |h| for R_c |h| (risk_metrics.py:293, :234).  h is a unit vector up to rounding on the
-// separating-direction path, where sqrt(1 + e) = 1 + e/2 - e^2/8 (+ O(e^3)) replaces the long
-// fp64 sqrt sequence (e = |h|^2 - 1 is exact there; the result is within 1 ulp of the correctly
-// rounded sqrt — it can differ only where 1 + e/2 is a rounding tie); any other h takes sqrt.
-__device__ __forceinline__ double norm_h(double h0, double h1) {
-  const double n2 = h0 * h0 + h1 * h1;
-  const double e = n2 - 1.0;
-  if (fabs(e) < 0x1p-40) return 1.0 + fma(-0.125 * e, e, 0.5 * e);  // uniform branch
-  return sqrt(n2);
-}
-
-// Per-unit status word (DRCVAR_UNIT_*): which of the reference's solver-failure branches the unit
-// took (core/risk_metrics.py:173-177,261-265: the LP status; :298-303,334-338: the sentinels) —
-// reported by the kernel itself, so no caller has to infer it from the sentinel's value.
-__device__ __forceinline__ int32_t failure_status(bool nonfinite, const Params& prm) {
-  return (nonfinite ? DRCVAR_UNIT_NONFINITE : 0) | (prm.unbounded ? DRCVAR_UNIT_UNBOUNDED : 0) |
-         (prm.epsilon < 0.0 ? DRCVAR_UNIT_DR_UNBOUNDED : 0);
 }
 
 // Offsets from the lower-tail statistics (wave 0, lane 0 writes).  L = tau + dsum / k.
@@ -972,7 +560,7 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
     h0 = e0;
     h1 = e1;
   } else {
-    separating_direction(mux, muy, e0, e1, deg_sq, &h0, &h1);
+    separating_direction<rsqrt_nr>(mux, muy, e0, e1, deg_sq, &h0, &h1);
   }
   if (bad || prm.unbounded) {  // solver failure, risk_metrics.py:298-303,334-338
     if constexpr (PEER) {
@@ -1230,7 +818,7 @@ safe_halfspace_stream_kernel(const double* __restrict__ samples, int64_t n_steps
     h0 = dp[0];
     h1 = dp[1];
   } else {
-    separating_direction(mux, muy, dp[0], dp[1], prm.degenerate_sq, &h0, &h1);
+    separating_direction<rsqrt_nr>(mux, muy, dp[0], dp[1], prm.degenerate_sq, &h0, &h1);
   }
   const double rch = prm.rc * norm_h(h0, h1);  // R_c |h|
   if (bad || prm.unbounded) {
@@ -1399,63 +987,6 @@ int dispatch(const Launch& L, int threads, int per) {
   }
   if (rc != DRCVAR_OK) return rc;
   return hipGetLastError() == hipSuccess ? DRCVAR_OK : DRCVAR_ERR_LAUNCH;
-}
-
-// Standard-normal quantile (P. J. Acklam's rational approximation, |rel err| < 1.2e-9) — only
-// positions the fast-path window, so its accuracy never affects results.
-double normal_quantile(double p) {
-  static const double a[] = {-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02,
-                             1.383577518672690e+02, -3.066479806614716e+01, 2.506628277459239e+00};
-  static const double b[] = {-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02,
-                             6.680131188771972e+01, -1.328068155288572e+01};
-  static const double c[] = {-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00,
-                             -2.549732539343734e+00, 4.374664141464968e+00, 2.938163982698783e+00};
-  static const double d[] = {7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00,
-                             3.754408661907416e+00};
-  p = std::fmin(std::fmax(p, 1e-12), 1.0 - 1e-12);
-  const double plow = 0.02425;
-  if (p < plow) {
-    const double q = std::sqrt(-2.0 * std::log(p));
-    return (((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) /
-           ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1.0);
-  }
-  if (p > 1.0 - plow) return -normal_quantile(1.0 - p);
-  const double q = p - 0.5, r = q * q;
-  return (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q /
-         (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1.0);
-}
-
-Params make_params(double rr, double ro, double alpha, double delta, double eps, int64_t n) {
-  Params p;
-  p.rc = rr + ro;
-  p.alpha = alpha;
-  p.delta = delta;
-  p.epsilon = eps;
-  p.eps_over_alpha = eps / alpha;
-  const double dn = static_cast<double>(n);
-  p.inv_n = 1.0 / dn;
-  p.k = alpha * dn;                      // exactly as the reference forms alpha * n_samples
-  p.inv_k = 1.0 / p.k;
-  p.unbounded = !(p.k <= dn);
-  const int64_t m = static_cast<int64_t>(std::floor(p.k));
-  p.rank = static_cast<uint32_t>(p.unbounded ? 0 : (m < n - 1 ? m : n - 1));
-  // window: the Gaussian alpha-quantile +- max(0.25 sd, 12 standard errors of the sample quantile)
-  const double a = std::fmin(std::fmax(alpha, 1e-12), 1.0 - 1e-12);
-  p.z_alpha = normal_quantile(a);
-  const double phi = std::exp(-0.5 * p.z_alpha * p.z_alpha) * 0.3989422804014327;
-  const double se = std::sqrt(a * (1.0 - a) / dn) / phi;
-  p.window_sd = std::fmax(0.25, 12.0 * se);
-  p.z_lo = p.z_alpha - p.window_sd;
-  double t = 1e-20;  // smallest t with sqrt(t) >= 1e-10 (sqrt is correctly rounded and monotone)
-  while (std::sqrt(t) >= 1e-10) t = std::nextafter(t, 0.0);
-  while (std::sqrt(t) < 1e-10) t = std::nextafter(t, 1.0);
-  p.degenerate_sq = t;
-  return p;
-}
-
-bool params_ok(double rr, double ro, double alpha, double delta, double eps) {
-  return std::isfinite(rr) && std::isfinite(ro) && std::isfinite(alpha) && alpha > 0.0 &&
-         std::isfinite(delta) && std::isfinite(eps);
 }
 
 int safe_halfspaces(const double* samples, int64_t n_obstacles, int64_t n_steps,

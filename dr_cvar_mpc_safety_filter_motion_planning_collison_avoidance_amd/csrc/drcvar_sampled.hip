@@ -26,10 +26,9 @@
 //
 // samples_out (optional): the kernel also stores the samples it drew; the record is the same bits.
 //
-// The wave reductions, the bucket map, the histogram scan and the candidate ranking are copies of
-// the helpers in drcvar_halfspace.hip: that file is left byte-identical because the committed
-// counter pass (profiles/kernel_time.json) is keyed to its hash.  Sharing them through an .inc is
-// a later change, together with a re-run of that pass.
+// The draw is the sampler's (drcvar_generator.inc) and the selection the stored form's
+// (drcvar_selection.inc); the direction alone differs on purpose, by one more Newton step of the
+// reciprocal square root (rsqrt_nr2).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -40,22 +39,10 @@
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kCap = 128;          // candidates ranked directly (per-wave region size in LDS)
-constexpr int kMaxValueIters = 3;  // value-linear refinements before switching to integer keys
 constexpr double kSentinel = 100.0;
 
-#include "drcvar_generator.inc"
-
-// Launch-uniform scalars of the halfspace mathematics (make_params, as the stored form makes them).
-struct Params {
-  double rc, alpha, delta, epsilon, eps_over_alpha;
-  double inv_n, k, inv_k;
-  double z_alpha, window_sd, z_lo, hist_scale;
-  uint32_t rank;
-  int unbounded;
-  double degenerate_sq;
-};
+#include "drcvar_generator.inc"  // the draw: Philox, Box-Muller, the LDS tables, draw_pair
+#include "drcvar_selection.inc"  // Params and the selection toolkit of the stored form
 
 // The draw's launch-uniform arguments (the sampler's SampleArgs, without its output).
 struct DrawArgs {
@@ -66,373 +53,6 @@ struct DrawArgs {
   PhiloxUniform pu;
   LogScale lg;
 };
-
-// The pair of samples of one Philox call: the sampler's draw_pair, restated (drcvar_sampling.hip).
-template <bool kIso>
-__device__ __forceinline__ void draw_pair(uint64_t g, const DrawArgs& a, double nx, double ny,
-                                          const double* s_turn, const double* s_log, double* x0,
-                                          double* y0, double* x1, double* y1) {
-  const Philox r = philox4x32_10(static_cast<uint32_t>(g), static_cast<uint32_t>(g >> 32), a.pu);
-  double c0, sn0, c1, sn1;
-  const double rad0 = sqrt_normal(scaled_neg2_log_u32(r.x[0], s_log, a.lg));
-  cos_sin_u32(r.x[1], s_turn, &c0, &sn0);
-  const double rad1 = sqrt_normal(scaled_neg2_log_u32(r.x[2], s_log, a.lg));
-  cos_sin_u32(r.x[3], s_turn, &c1, &sn1);
-  if constexpr (kIso) {
-    *x0 = fma(rad0, c0, nx);
-    *y0 = fma(rad0, sn0, ny);
-    *x1 = fma(rad1, c1, nx);
-    *y1 = fma(rad1, sn1, ny);
-  } else {
-    const double z00 = rad0 * c0, z01 = rad0 * sn0, z10 = rad1 * c1, z11 = rad1 * sn1;
-    *x0 = fma(a.l00, z00, nx);
-    *y0 = fma(a.l10, z00, fma(a.l11, z01, ny));
-    *x1 = fma(a.l00, z10, nx);
-    *y1 = fma(a.l10, z10, fma(a.l11, z11, ny));
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// copies of drcvar_halfspace.hip's device helpers (see the note at the top)
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double rsqrt_nr(double x) {
-  const double y = __builtin_amdgcn_rsq(x);
-  return y * fma(-0.5 * x * y, y, 1.5);
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
-constexpr int kDppQuadXor1 = 0xB1;     // quad_perm [1,0,3,2]
-constexpr int kDppQuadXor2 = 0x4E;     // quad_perm [2,3,0,1]
-constexpr int kDppHalfMirror = 0x141;  // row_half_mirror
-constexpr int kDppMirror = 0x140;      // row_mirror
-
-struct OpAdd {
-  __device__ static double f(double a, double b) { return a + b; }
-};
-struct OpMin {
-  __device__ static double f(double a, double b) { return fmin(a, b); }
-};
-struct OpMax {
-  __device__ static double f(double a, double b) { return fmax(a, b); }
-};
-
-__device__ __forceinline__ double uniform_f64(double v) {
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-
-template <class Op>
-__device__ __forceinline__ double swap_combine16(double v) {
-  const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(v), __double2loint(v), false, false);
-  const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(v), __double2hiint(v), false, false);
-  return Op::f(__hiloint2double(hi[0], lo[0]), __hiloint2double(hi[1], lo[1]));
-}
-template <class Op>
-__device__ __forceinline__ double swap_combine32(double v) {
-  const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(v), __double2loint(v), false, false);
-  const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(v), __double2hiint(v), false, false);
-  return Op::f(__hiloint2double(hi[0], lo[0]), __hiloint2double(hi[1], lo[1]));
-}
-
-// Uniform across the wave, bitwise: every lane evaluates the same tree.  All 64 lanes active.
-template <class Op>
-__device__ __forceinline__ double wave_reduce(double v) {
-  v = Op::f(v, dpp_f64<kDppQuadXor1>(v));
-  v = Op::f(v, dpp_f64<kDppQuadXor2>(v));
-  v = Op::f(v, dpp_f64<kDppHalfMirror>(v));
-  v = Op::f(v, dpp_f64<kDppMirror>(v));
-  return uniform_f64(swap_combine32<Op>(swap_combine16<Op>(v)));
-}
-
-// Sum of NW per-wave partials read by every thread (broadcast LDS reads), fixed pairwise tree.
-template <int NW>
-__device__ __forceinline__ double sum_partials(const double* p) {
-  double v[NW];
-#pragma unroll
-  for (int w = 0; w < NW; ++w) v[w] = p[w];
-#pragma unroll
-  for (int stride = 1; stride < NW; stride *= 2)
-#pragma unroll
-    for (int w = 0; w + stride < NW; w += 2 * stride) v[w] = v[w] + v[w + stride];
-  return uniform_f64(v[0]);
-}
-
-template <class Op>
-__device__ __forceinline__ double identity_of();
-template <>
-__device__ __forceinline__ double identity_of<OpAdd>() { return 0.0; }
-template <>
-__device__ __forceinline__ double identity_of<OpMin>() { return INFINITY; }
-template <>
-__device__ __forceinline__ double identity_of<OpMax>() { return -INFINITY; }
-
-// Workgroup reduction of one value; `slot` is LDS scratch of NW doubles owned by the call site.
-template <class Op, int NW>
-__device__ __forceinline__ double block_reduce(double v, double* slot) {
-  v = wave_reduce<Op>(v);
-  if constexpr (NW > 1) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int w = threadIdx.x / kWave;
-    if (lane == 0) slot[w] = v;
-    __syncthreads();
-    v = wave_reduce<Op>(lane < NW ? slot[lane] : identity_of<Op>());
-  }
-  return v;
-}
-
-// order-preserving map double -> uint64 (total order on non-NaN values)
-__device__ __forceinline__ uint64_t f64_key(double d) {
-  const uint64_t u = static_cast<uint64_t>(__double_as_longlong(d));
-  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-
-// Monotone (non-decreasing) map of the candidate interval [lo, hi] onto NB histogram bins.
-template <int LOG_NB>
-struct BucketMap {
-  static constexpr int NB = 1 << LOG_NB;
-  bool value_mode;
-  double lo, scale;
-  uint64_t klo;
-  int shift;
-
-  __device__ __forceinline__ void init_range(double lo_, double hi_, int iter) {
-    lo = lo_;
-    const double range = hi_ - lo_;
-    scale = static_cast<double>(NB) / range;
-    value_mode = iter < kMaxValueIters && range > 0.0 && scale < 1e300 && range * scale >= 1.0;
-    klo = f64_key(lo_);
-    const uint64_t diff = f64_key(hi_) - klo;  // >= 1 when hi > lo
-    const int bits = 64 - __builtin_clzll(diff | 1ull);
-    shift = bits > LOG_NB ? bits - LOG_NB : 0;
-  }
-  __device__ __forceinline__ int operator()(double d) const {
-    if (value_mode) {
-      const double t = fmin(fmax((d - lo) * scale, 0.0), static_cast<double>(NB - 1));
-      return static_cast<int>(t);
-    }
-    return static_cast<int>((f64_key(d) - klo) >> shift);  // key mode: lo <= d <= hi only
-  }
-};
-
-struct ScanResult {
-  int bin;
-  uint32_t below, cnt;
-  bool found;  // false when the histogram holds fewer than rr + 1 samples
-};
-
-// Histogram storage: lane l of a scanning wave owns bins [l B, (l + 1) B), B = NB / 64; one padding
-// word after every B bins makes the owner reads conflict-free.
-template <int NB>
-__device__ __forceinline__ int hist_slot(int bin) {  // bin >= 0
-  constexpr unsigned B = NB / kWave;
-  const unsigned b = static_cast<unsigned>(bin);
-  return static_cast<int>(b + b / B);
-}
-template <int NB>
-constexpr int hist_words() {
-  return NB + kWave;
-}
-
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x, int lane) {
-  constexpr int kRowShr1 = 0x111, kRowShr2 = 0x112, kRowShr4 = 0x114, kRowShr8 = 0x118;
-  int v = static_cast<int>(x);
-  v += __builtin_amdgcn_update_dpp(0, v, kRowShr1, 0xF, 0xF, true);
-  v += __builtin_amdgcn_update_dpp(0, v, kRowShr2, 0xF, 0xF, true);
-  v += __builtin_amdgcn_update_dpp(0, v, kRowShr4, 0xF, 0xF, true);
-  v += __builtin_amdgcn_update_dpp(0, v, kRowShr8, 0xF, 0xF, true);
-  const int r0 = __builtin_amdgcn_readlane(v, 15);
-  const int r1 = __builtin_amdgcn_readlane(v, 31);
-  const int r2 = __builtin_amdgcn_readlane(v, 47);
-  const int row = lane >> 4;
-  v += (row >= 1 ? r0 : 0) + (row >= 2 ? r1 : 0) + (row >= 3 ? r2 : 0);
-  return static_cast<uint32_t>(v);
-}
-
-// Any wave: the bin holding the sample of rank rr (0-based) and the counts below / inside it.
-// Result is uniform across the wave.
-template <int NB>
-__device__ __forceinline__ ScanResult scan_bins(const uint32_t* hist, uint32_t rr, int lane) {
-  constexpr int B = NB / kWave;  // contiguous bins per lane
-  uint32_t h[B];
-  const uint32_t* mine = hist + lane * (B + 1);
-#pragma unroll
-  for (int q = 0; q < B; ++q) h[q] = mine[q];
-  uint32_t s = 0;
-#pragma unroll
-  for (int q = 0; q < B; ++q) s += h[q];
-  const uint32_t incl = wave_inclusive_scan(s, lane);
-  const unsigned long long hit = __ballot(incl > rr);
-  if (hit == 0ull) return ScanResult{0, 0u, 0u, false};
-  const int owner = __ffsll(static_cast<long long>(hit)) - 1;  // uniform
-  uint32_t cum = incl - s;
-  int bin = lane * B + B - 1;
-  uint32_t below = 0, cnt = 0;
-  bool done = false;
-#pragma unroll
-  for (int q = 0; q < B; ++q) {
-    const bool take = !done && cum + h[q] > rr;
-    bin = take ? lane * B + q : bin;
-    below = take ? cum : below;
-    cnt = take ? h[q] : cnt;
-    done = done || take;
-    cum += h[q];
-  }
-  return ScanResult{__builtin_amdgcn_readlane(bin, owner),
-                    static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(below), owner)),
-                    static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cnt), owner)),
-                    true};
-}
-
-__device__ __forceinline__ bool in_range(double d, double lo, double hi) {
-  return lo <= d && d <= hi;  // false for NaN
-}
-
-// MeanSafeHalfspace (core/halfspaces.py:84-94): direction from the ORIGIN, offset
-// -(h.mu - R_c |h|), with compute_separating_vector's [1, 0] fallback
-__device__ __forceinline__ void mean_halfspace(double mux, double muy, double rc, double* m0,
-                                               double* m1, double* g) {
-  const double nm = sqrt(mux * mux + muy * muy);
-  const bool degenerate = nm < 1e-10;
-  *m0 = degenerate ? 1.0 : mux / nm;
-  *m1 = degenerate ? 0.0 : muy / nm;
-  *g = -((*m0 * mux + *m1 * muy) - rc * sqrt(*m0 * *m0 + *m1 * *m1));
-}
-
-// d_i = h . xi_i (core/risk_metrics.py:145,233: h @ samples.T)
-__device__ __forceinline__ double project(double h0, double h1, double x, double y) {
-  return fma(h0, x, h1 * y);
-}
-
-// Value-linear position in the window: t(d) = d scale + off (one fma, rounded once, so monotone
-// non-decreasing in d for any scale > 0).  Below the window t < 0, inside 0 <= t < NB, above (and
-// the +inf padding) t >= NB.
-struct LinearMap {
-  double scale, off;
-  __device__ __forceinline__ double operator()(double d) const { return fma(d, scale, off); }
-};
-
-// Per-wave ordered compaction step: append the candidates of one row to this wave's LDS region.
-__device__ __forceinline__ void append_candidate(double* region, uint32_t& wbase, bool is_cand,
-                                                 double v, unsigned long long lt_mask) {
-  const unsigned long long ballot = __ballot(is_cand);
-  if (is_cand) region[wbase + __popcll(ballot & lt_mask)] = v;
-  wbase += static_cast<uint32_t>(__popcll(ballot));
-}
-
-// Wave 0 (all lanes active): tau = the candidate of rank rr among the c <= kCap candidates held in
-// per-wave regions cand[w kCap + i], i < wcount[w] (global order: wave, then position — fixed), and
-// s_cand = sum over candidates below tau of (cand - tau), in candidate order.
-template <int NW, int Q>
-__device__ __forceinline__ double rank_candidates_q(const double* cand, uint32_t cw, uint32_t c,
-                                                    uint32_t rr, int lane, double* s_cand) {
-  int slot[2] = {-1, -1};
-  uint32_t acc = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    const uint32_t nw = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cw), w));
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      const uint32_t g = lane + q * kWave;
-      if (g >= acc && g < acc + nw) slot[q] = w * kCap + static_cast<int>(g - acc);
-    }
-    acc += nw;
-  }
-  double mine[2] = {NAN, NAN};  // candidates g = lane, lane + 64
-#pragma unroll
-  for (int q = 0; q < Q; ++q)
-    if (slot[q] >= 0) mine[q] = cand[slot[q]];
-  uint32_t less[2] = {0u, 0u}, eq[2] = {0u, 0u};
-  double sl[2] = {0.0, 0.0};
-  const uint32_t c0 = c < kWave ? c : kWave;
-  for (uint32_t i = 0; i < c0; ++i) {  // uniform trip count
-    const double z = readlane_f64(mine[0], static_cast<int>(i));
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      const bool lt = z < mine[q];
-      less[q] += lt ? 1u : 0u;
-      eq[q] += (z == mine[q]) ? 1u : 0u;
-      sl[q] += lt ? z - mine[q] : 0.0;
-    }
-  }
-  for (uint32_t i = kWave; Q == 2 && i < c; ++i) {
-    const double z = readlane_f64(mine[1], static_cast<int>(i - kWave));
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      const bool lt = z < mine[q];
-      less[q] += lt ? 1u : 0u;
-      eq[q] += (z == mine[q]) ? 1u : 0u;
-      sl[q] += lt ? z - mine[q] : 0.0;
-    }
-  }
-  bool found = false;
-  double found_v = 0.0, found_s = 0.0;
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    if (lane + q * kWave < c && less[q] <= rr && rr < less[q] + eq[q]) {
-      found = true;
-      found_v = mine[q];
-      found_s = sl[q];
-    }
-  }
-  const unsigned long long fb = __ballot(found);
-  const int src = __ffsll(static_cast<long long>(fb)) - 1;
-  *s_cand = readlane_f64(found_s, src);
-  return readlane_f64(found_v, src);
-}
-template <int NW>
-__device__ __forceinline__ double rank_candidates(const double* cand, uint32_t cw, uint32_t c,
-                                                  uint32_t rr, int lane, double* s_cand) {
-  return c <= static_cast<uint32_t>(kWave) ? rank_candidates_q<NW, 1>(cand, cw, c, rr, lane, s_cand)
-                                           : rank_candidates_q<NW, 2>(cand, cw, c, rr, lane, s_cand);
-}
-
-// 1/sqrt(x) within 1.5 units of 2^-53: rsqrt_nr leaves 2.5 roundings plus 1.5 e^2 of the hardware
-// seed's error e (about 5 units in all, measured on a unit with |h1| = 0.8: h1 five units off, more
-// than the four the reference's bound on h allots to the subtraction, the rsqrt and the product).
-// One more Newton step in residual form: r = x y is rounded once, 1 - r y comes exact out of the
-// fma, and y (1 + e / 2) rounds once.
-__device__ __forceinline__ double rsqrt_nr2(double x) {
-  const double y = rsqrt_nr(x);
-  const double e = fma(-(x * y), y, 1.0);
-  return fma(0.5 * e, y, y);
-}
-
-// compute_separating_vector(ego, mu) (core/geometry.py:35-53): (mu - ego) / |mu - ego|, [1, 0]
-// below 1e-10 (rsqrt + Newton).
-__device__ __forceinline__ void separating_direction(double mux, double muy, double e0, double e1,
-                                                     double deg_sq, double* h0, double* h1) {
-  const double dx = mux - e0, dy = muy - e1;
-  const double n2 = dx * dx + dy * dy;
-  const double inv = n2 == INFINITY ? 0.0 : rsqrt_nr2(n2);
-  const bool degenerate = n2 < deg_sq;
-  *h0 = degenerate ? 1.0 : dx * inv;
-  *h1 = degenerate ? 0.0 : dy * inv;
-}
-
-// |h| for R_c |h| (risk_metrics.py:293, :234): sqrt(1 + e) = 1 + e/2 - e^2/8 near a unit vector.
-__device__ __forceinline__ double norm_h(double h0, double h1) {
-  const double n2 = h0 * h0 + h1 * h1;
-  const double e = n2 - 1.0;
-  if (fabs(e) < 0x1p-40) return 1.0 + fma(-0.125 * e, e, 0.5 * e);  // uniform branch
-  return sqrt(n2);
-}
-
-// Per-unit status word (DRCVAR_UNIT_*), as the stored form reports it.
-__device__ __forceinline__ int32_t failure_status(bool nonfinite, const Params& prm) {
-  return (nonfinite ? DRCVAR_UNIT_NONFINITE : 0) | (prm.unbounded ? DRCVAR_UNIT_UNBOUNDED : 0) |
-         (prm.epsilon < 0.0 ? DRCVAR_UNIT_DR_UNBOUNDED : 0);
-}
 
 // The whole record by one lane, plain stores.
 __device__ __forceinline__ void store_record(double* rec, double mux, double muy, double rc,
@@ -468,16 +88,17 @@ __device__ __forceinline__ void select_from_registers(const double (&d)[Q], uint
   const int wave = tid / kWave;
   __syncthreads();  // the window path's readers of hist are done
 
-  double vmin = INFINITY, vmax = -INFINITY;
+  double vmin[1] = {INFINITY}, vmax[1] = {-INFINITY};
 #pragma unroll
   for (int q = 0; q < Q; ++q) {
     if ((vmask >> q) & 1u) {
-      vmin = fmin(vmin, d[q]);
-      vmax = fmax(vmax, d[q]);
+      vmin[0] = fmin(vmin[0], d[q]);
+      vmax[0] = fmax(vmax[0], d[q]);
     }
   }
-  double lo = block_reduce<OpMin, NW>(vmin, red_rng);
-  double hi = block_reduce<OpMax, NW>(vmax, red_rng + NW);
+  block_reduce<OpMin, NW, 1>(vmin, red_rng);
+  block_reduce<OpMax, NW, 1>(vmax, red_rng + NW);
+  double lo = vmin[0], hi = vmax[0];
   if (lo == hi) {  // every sample projects to one value: no tail below it
     *tau_out = lo;
     *dsum_out = 0.0;
@@ -504,18 +125,20 @@ __device__ __forceinline__ void select_from_registers(const double (&d)[Q], uint
     c = sr.cnt;
     have_bin = true;
     if (c <= kCap) break;
-    double rmin = INFINITY, rmax = -INFINITY;
+    double rmin[1] = {INFINITY}, rmax[1] = {-INFINITY};
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
       const double v = ((vmask >> q) & 1u) ? d[q] : NAN;
       if (in_range(v, lo, hi) && map(v) == bin) {
-        rmin = fmin(rmin, v);
-        rmax = fmax(rmax, v);
+        rmin[0] = fmin(rmin[0], v);
+        rmax[0] = fmax(rmax[0], v);
       }
     }
     __syncthreads();  // all waves have scanned hist before it is cleared again
-    lo = block_reduce<OpMin, NW>(rmin, red_rng);
-    hi = block_reduce<OpMax, NW>(rmax, red_rng + NW);
+    block_reduce<OpMin, NW, 1>(rmin, red_rng);
+    block_reduce<OpMax, NW, 1>(rmax, red_rng + NW);
+    lo = rmin[0];
+    hi = rmax[0];
     have_bin = false;
     if (lo == hi) {
       tau_known = true;
@@ -654,7 +277,7 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
   // a non-finite nominal position or factor makes a sum non-finite: solver failure
   const bool bad = !(std::isfinite(sx) && std::isfinite(sy));
   double h0, h1;
-  separating_direction(mux, muy, e0, e1, prm.degenerate_sq, &h0, &h1);
+  separating_direction<rsqrt_nr2>(mux, muy, e0, e1, prm.degenerate_sq, &h0, &h1);
   if (bad || prm.unbounded) {  // risk_metrics.py:298-303,334-338
     if (tid == 0) {
       const double r = prm.rc * norm_h(h0, h1);
@@ -768,78 +391,6 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-// LogScale for lam (see drcvar_generator.inc), as the sampler makes it.
-LogScale make_log_scale(double lam) {
-  LogScale c{};
-  c.lam = lam;
-  c.q0 = lam * (1.0 / 192.0);
-  c.q1 = lam * (1.0 / 80.0);
-  c.q2 = lam * (1.0 / 32.0);
-  c.q3 = lam * (1.0 / 12.0);
-  c.q4 = lam * 0.25;
-  const long double e2 = -2.0L * static_cast<long double>(lam) * 0.693147180559945309417232121458176568L;
-  double eh = static_cast<double>(e2);
-  uint64_t bits;
-  std::memcpy(&bits, &eh, sizeof bits);
-  bits &= ~uint64_t{0x7f};  // 53 - 7 = 46 significant bits
-  std::memcpy(&eh, &bits, sizeof bits);
-  c.eh = eh;
-  c.el = static_cast<double>(e2 - static_cast<long double>(eh));
-  return c;
-}
-
-// Standard-normal quantile (P. J. Acklam's rational approximation) — only positions the window.
-double normal_quantile(double p) {
-  static const double a[] = {-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02,
-                             1.383577518672690e+02, -3.066479806614716e+01, 2.506628277459239e+00};
-  static const double b[] = {-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02,
-                             6.680131188771972e+01, -1.328068155288572e+01};
-  static const double c[] = {-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00,
-                             -2.549732539343734e+00, 4.374664141464968e+00, 2.938163982698783e+00};
-  static const double d[] = {7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00,
-                             3.754408661907416e+00};
-  p = std::fmin(std::fmax(p, 1e-12), 1.0 - 1e-12);
-  const double plow = 0.02425;
-  if (p < plow) {
-    const double q = std::sqrt(-2.0 * std::log(p));
-    return (((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) /
-           ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1.0);
-  }
-  if (p > 1.0 - plow) return -normal_quantile(1.0 - p);
-  const double q = p - 0.5, r = q * q;
-  return (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q /
-         (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1.0);
-}
-
-// The stored form's make_params (drcvar_halfspace.hip): the same z_lo, window_sd and rank.
-Params make_params(double rr, double ro, double alpha, double delta, double eps, int64_t n) {
-  Params p{};
-  p.rc = rr + ro;
-  p.alpha = alpha;
-  p.delta = delta;
-  p.epsilon = eps;
-  p.eps_over_alpha = eps / alpha;
-  const double dn = static_cast<double>(n);
-  p.inv_n = 1.0 / dn;
-  p.k = alpha * dn;  // exactly as the reference forms alpha * n_samples
-  p.inv_k = 1.0 / p.k;
-  p.unbounded = !(p.k <= dn);
-  const int64_t m = static_cast<int64_t>(std::floor(p.k));
-  p.rank = static_cast<uint32_t>(p.unbounded ? 0 : (m < n - 1 ? m : n - 1));
-  // window: the Gaussian alpha-quantile +- max(0.25 sd, 12 standard errors of the sample quantile)
-  const double a = std::fmin(std::fmax(alpha, 1e-12), 1.0 - 1e-12);
-  p.z_alpha = normal_quantile(a);
-  const double phi = std::exp(-0.5 * p.z_alpha * p.z_alpha) * 0.3989422804014327;
-  const double se = std::sqrt(a * (1.0 - a) / dn) / phi;
-  p.window_sd = std::fmax(0.25, 12.0 * se);
-  p.z_lo = p.z_alpha - p.window_sd;
-  double t = 1e-20;  // smallest t with sqrt(t) >= 1e-10 (sqrt is correctly rounded and monotone)
-  while (std::sqrt(t) >= 1e-10) t = std::nextafter(t, 0.0);
-  while (std::sqrt(t) < 1e-10) t = std::nextafter(t, 1.0);
-  p.degenerate_sq = t;
-  return p;
-}
-
 // Launch plans: (threads, Philox pairs per thread, log2 bins); a plan holds 2 threads pairs
 // samples.  Nothing has to be in flight from memory, so the blocks are wide and a thread holds few
 // pairs: x, y and the generator's temporaries stay in registers.
@@ -910,8 +461,7 @@ extern "C" int drcvar_sampled_halfspaces_f64(
   if (n_obstacles < 0 || n_steps < 0 || n_samples < 0 || unit_begin < 0 || unit_count < 0)
     return DRCVAR_ERR_INVALID_ARGUMENT;
   if (!(l00 == l00) || !(l10 == l10) || !(l11 == l11)) return DRCVAR_ERR_INVALID_ARGUMENT;
-  if (!(std::isfinite(robot_radius) && std::isfinite(obstacle_radius) && std::isfinite(alpha) &&
-        alpha > 0.0 && std::isfinite(delta) && std::isfinite(epsilon)))
+  if (!params_ok(robot_radius, obstacle_radius, alpha, delta, epsilon))
     return DRCVAR_ERR_INVALID_ARGUMENT;
   // the sampler's grid limits, and the register plans' sample count
   if (n_obstacles > (int64_t{1} << 40) || n_steps > (int64_t{1} << 40) ||

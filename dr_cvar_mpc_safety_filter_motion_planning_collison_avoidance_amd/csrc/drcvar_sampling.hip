@@ -91,34 +91,6 @@ __device__ __forceinline__ void put_sample(double* p, double x, double y) {
   }
 }
 
-// The pair of samples of one Philox call (counter g, the unit's nominal point): sample p from the
-// call's first (radius, angle) words, sample p + P from its second.  kIso: the covariance is l^2 I
-// and the log already carries lam = l^2 (LogScale), so a sample is nominal + radius (cos, sin);
-// otherwise nominal + L z as an fma chain (the mirror rounds ny + (l10 z0 + l11 z1): a few ulp apart).
-template <bool kIso>
-__device__ __forceinline__ void draw_pair(uint64_t g, const SampleArgs& a, double nx, double ny,
-                                          const double* s_turn, const double* s_log, double* x0,
-                                          double* y0, double* x1, double* y1) {
-  const Philox r = philox4x32_10(static_cast<uint32_t>(g), static_cast<uint32_t>(g >> 32), a.pu);
-  double c0, sn0, c1, sn1;
-  const double rad0 = sqrt_normal(scaled_neg2_log_u32(r.x[0], s_log, a.lg));
-  cos_sin_u32(r.x[1], s_turn, &c0, &sn0);
-  const double rad1 = sqrt_normal(scaled_neg2_log_u32(r.x[2], s_log, a.lg));
-  cos_sin_u32(r.x[3], s_turn, &c1, &sn1);
-  if constexpr (kIso) {
-    *x0 = fma(rad0, c0, nx);
-    *y0 = fma(rad0, sn0, ny);
-    *x1 = fma(rad1, c1, nx);
-    *y1 = fma(rad1, sn1, ny);
-  } else {
-    const double z00 = rad0 * c0, z01 = rad0 * sn0, z10 = rad1 * c1, z11 = rad1 * sn1;
-    *x0 = fma(a.l00, z00, nx);
-    *y0 = fma(a.l10, z00, fma(a.l11, z01, ny));
-    *x1 = fma(a.l00, z10, nx);
-    *y1 = fma(a.l10, z10, fma(a.l11, z11, ny));
-  }
-}
-
 // 16-B store at a uniform base (SGPRs) + a 32-bit lane offset: global_store_dwordx4 in its
 // saddr form, one v_add per pair for the offset and no 64-bit address arithmetic.  (A buffer-store
 // form with the pair's offset in soffset needed no VALU at all, but on gfx950 the VALU that next
@@ -194,28 +166,6 @@ __global__ __launch_bounds__(kBlock) void sample_kernel(SampleArgs a) {
       if (pidx + pairs < a.N) put_sample<kPacked, kNT>(dst + (pidx + pairs) * sn, x1, y1);
     }
   }
-}
-
-// LogScale for lam (see drcvar_generator.inc): the Horner coefficients of -P/2 in r2
-// (1/192, 1/80, 1/32, 1/12, 1/4) times lam, and -2 lam ln 2 split into a 46-bit head (e * eh exact
-// for |e| <= 33) and a tail, from an extended-precision product.
-LogScale make_log_scale(double lam) {
-  LogScale c{};
-  c.lam = lam;
-  c.q0 = lam * (1.0 / 192.0);
-  c.q1 = lam * (1.0 / 80.0);
-  c.q2 = lam * (1.0 / 32.0);
-  c.q3 = lam * (1.0 / 12.0);
-  c.q4 = lam * 0.25;
-  const long double e2 = -2.0L * static_cast<long double>(lam) * 0.693147180559945309417232121458176568L;
-  double eh = static_cast<double>(e2);
-  uint64_t bits;
-  std::memcpy(&bits, &eh, sizeof bits);
-  bits &= ~uint64_t{0x7f};  // 53 - 7 = 46 significant bits
-  std::memcpy(&eh, &bits, sizeof bits);
-  c.eh = eh;
-  c.el = static_cast<double>(e2 - static_cast<long double>(eh));
-  return c;
 }
 
 int launch_samples(const double* nominal, int64_t n_obstacles, int64_t n_steps, int64_t nom_so,

@@ -276,9 +276,9 @@ def sampled_halfspaces(nominal: torch.Tensor, ego: torch.Tensor, n_samples: int,
     The draw is bit for bit ``sample_trajectories_device`` / ``sample_units_device`` for the same
     seed and stream offset, and the record agrees with ``safe_halfspaces`` on that draw to
     rounding (a summation order of its own).  Measured against sampler + ``safe_halfspaces`` on
-    one stream (profiles/sampled/sampled_times.json): C3 (10 x 20 x 1000) 6.4 us
-    against 16.5 us, C4 (64 x 30 x 5000) 59.7 us against 77.6 us; C5 (256 x 50 x 10000) is NOT
-    faster, 0.781 ms against 0.722 ms — above 8192 samples a unit takes a whole CU's registers, so
+    one stream (profiles/sampled/sampled_times.json): C3 (10 x 20 x 1000) 6.5 us
+    against 17.3 us, C4 (64 x 30 x 5000) 58.3 us against 74.5 us; C5 (256 x 50 x 10000) is NOT
+    faster, 0.774 ms against 0.720 ms — above 8192 samples a unit takes a whole CU's registers, so
     nothing overlaps its selection — and saves only the 2.05 GB buffer.  Nothing dispatches
     between the two forms, the caller chooses.
     """

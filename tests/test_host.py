@@ -138,12 +138,38 @@ def test_product_loader_reads_no_environment():
 
 def test_profile_evidence_key_covers_the_unit_and_its_includes():
     """bench.py's roofline uses committed kernel-time evidence only while _native.source_key()
-    matches: the key hashes the halfspace unit, the headers it includes, the toolchain and its
-    flags -- not the MPC or sampler headers, whose edits do not change the halfspace kernel."""
+    matches: the key hashes the halfspace unit, the headers and the selection toolkit it includes,
+    the toolchain and its flags -- not the MPC or sampler headers nor the generator, whose edits do
+    not change the halfspace kernel."""
     import os
     from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd import _native
     src = os.path.join(_native.PKG_DIR, "csrc", "drcvar_halfspace.hip")
     incs = [os.path.basename(f) for f in _native._quoted_includes(src)]
-    assert incs == ["drcvar_exchange.h", "drcvar_halfspace.h"]
+    assert incs == ["drcvar_exchange.h", "drcvar_halfspace.h", "drcvar_selection.inc"]
+    assert "drcvar_generator.inc" not in incs
+    sampled = os.path.join(_native.PKG_DIR, "csrc", "drcvar_sampled.hip")
+    sampled_incs = [os.path.basename(f) for f in _native._quoted_includes(sampled)]
+    assert {"drcvar_generator.inc", "drcvar_selection.inc"} <= set(sampled_incs)
     assert _native.source_key() == _native.source_key("drcvar_halfspace.hip")
     assert _native.source_key("drcvar_mpc.hip") != _native.source_key()
+
+
+def test_shared_kernel_helpers_are_defined_once():
+    """The selection toolkit (drcvar_selection.inc) and the generator glue (drcvar_generator.inc)
+    are shared by inclusion: a fix to the ranking or the bucket map is made in one place.  Each of
+    these helpers is defined in exactly one file under csrc/."""
+    import glob
+    import os
+    import re
+    from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd import _native
+    files = sorted(glob.glob(os.path.join(_native.PKG_DIR, "csrc", "*")))
+    text = {os.path.basename(f): open(f).read() for f in files}
+    assert "drcvar_selection.inc" in text and "drcvar_generator.inc" in text
+    functions = ["make_log_scale", "make_params", "normal_quantile", "draw_pair", "wave_reduce",
+                 "scan_loaded_bins", "rank_candidates_q", "f64_key"]
+    # a definition: the name, its parameter list, then the opening brace (a call ends in ; or ,)
+    patterns = {n: rf"\b{n}\s*\([^;{{}}]*\)\s*(const\s*)?\{{" for n in functions}
+    patterns["struct BucketMap"] = r"\bstruct\s+BucketMap\s*\{"
+    for name, pat in patterns.items():
+        owners = [f for f, s in text.items() for _ in re.finditer(pat, s)]
+        assert len(owners) == 1, (name, owners)
