@@ -45,8 +45,9 @@ typedef double dbl2 __attribute__((ext_vector_type(2)));
 
 #ifdef DRCVAR_STAMPS
 // diagnostic build only: per-unit shader-clock stamps at phase boundaries (wave 0)
-#ifdef DRCVAR_STAMPS_WAVES  // + per-wave stamps (slots 8 + 4j + wave) around the load phase
-constexpr int kStampUnits = 16384, kStamps = 16;
+#ifdef DRCVAR_STAMPS_WAVES  // + per-wave stamps (slots 8 + 4j + wave): j = 0, 1 around the load
+                            // phase, j = 2 at the end of every wave (which wave exits last)
+constexpr int kStampUnits = 16384, kStamps = 24;
 #else
 constexpr int kStampUnits = 16384, kStamps = 8;
 #endif
@@ -267,6 +268,7 @@ __device__ __forceinline__ uint32_t wave_counts(const uint32_t* wcount, int lane
 // Makes a loaded value available at this point (an empty asm that consumes it): keeps the compiler
 // from sinking independent LDS loads past a branch or a wait, so they share one round trip.
 __device__ __forceinline__ void lds_values_ready(uint32_t v) { asm volatile("" ::"v"(v)); }
+__device__ __forceinline__ void lds_values_ready(double v) { asm volatile("" ::"v"(v)); }
 
 // Exact selection for the units the register fast path does not finish (degenerate moments, or a
 // first-pass bucket with more than kCap samples).  It re-reads the unit's samples (L2/MALL-hot)
@@ -670,11 +672,19 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
     uint32_t wbase = 0;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const uint32_t ubin = static_cast<uint32_t>(bin);
+    // The express finish: of a bucket of c <= 64 / NW candidates (every wave knows c from the
+    // scan) no wave holds more than E = 64 / NW, so wave w writes its candidates to the segment
+    // cand[w * E ..) instead of its region cand[w * kCap ..): all of the unit's candidates lie in
+    // cand[0 .. 64), in the ranking's order, and wave 0 reads them — one per lane — in the same
+    // batch as the counts and the tail partials: no slot computation and no second, dependent LDS
+    // round trip ahead of the ranking.  Larger buckets keep the regions (a uniform branch on c).
+    const bool express = c <= static_cast<uint32_t>(kWave / NW);
+    double* const cregion = cand + wave * (express ? kWave / NW : kCap);
 #pragma unroll
     for (int j = 0; j < P; ++j) {
       const uint32_t cj = (code[j / 2] >> (16 * (j % 2))) & 0xFFFFu;
       sq += cj < ubin ? d[j] - mu_d : 0.0;
-      append_candidate(cand + wave * kCap, wbase, cj == ubin, d[j], lt_mask);
+      append_candidate(cregion, wbase, cj == ubin, d[j], lt_mask);
     }
     if constexpr (kPilot) {
       // small plans: this lane's tail partial goes to LDS unreduced; wave 0 reduces the four waves'
@@ -694,17 +704,29 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
     DRCVAR_STAMP(6);
     if (wave != 0) {
       if (!PEER && wave == 1) write_mean_halfspace(rec, mux, muy, prm.rc, lane);
+      DRCVAR_STAMP_WAVE(2);  // diagnostic build: this wave's end
       return;
     }
-    // the per-wave candidate counts are read in the same batch as the tail partials (the ranking
-    // needs them for its candidate addresses; read inside it, they were a second LDS round trip)
-    const uint32_t cw = wave_counts<NW>(wcount, lane);
+    // One batch of LDS reads: the per-wave candidate counts (cw: lane w < NW holds wave w's, the
+    // region ranking's input — read by every lane, lane l wave l % NW's, which needs no exec mask;
+    // cx: lane l holds the count of the wave whose segment l lies in, the express ranking's
+    // validity test), this lane's candidate of the segment layout (unused, any value, on a larger
+    // bucket) and the tail partials.
+    const uint32_t cw = wcount[lane & (NW - 1)];
+    const uint32_t cx = wcount[lane / (kWave / NW)];
+    const double mine = cand[lane];
     double s_below;
     if constexpr (kPilot) {
       double tl[NW];
 #pragma unroll
       for (int w = 0; w < NW; ++w) tl[w] = lane_tail[w * kWave + lane];
+      // R_c |h| while the reads are in flight: off the histogram's critical path, and off the
+      // finish's (computed after the tail's reduction, it stood in series with the ranking)
+      rch = prm.rc * norm_h(h0, h1);
+      lds_values_ready(rch);
       lds_values_ready(cw);
+      lds_values_ready(cx);
+      lds_values_ready(mine);
       double t = tl[0];
 #pragma unroll
       for (int w = 1; w < NW; ++w) t += tl[w];
@@ -712,10 +734,15 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
     } else {
       s_below = sum_partials<NW>(red_tail);
       lds_values_ready(cw);
+      lds_values_ready(cx);
+      lds_values_ready(mine);
+      rch = prm.rc * norm_h(h0, h1);  // R_c |h|: off the histogram's critical path
     }
-    rch = prm.rc * norm_h(h0, h1);  // R_c |h|: off the histogram's critical path
     double s_cand;
-    tau = rank_candidates<NW>(cand, cw, c, rr, lane, &s_cand);
+    if (express) [[likely]]
+      tau = rank_candidates_express<NW>(mine, cx, rr, lane, &s_cand);
+    else
+      tau = rank_candidates<NW>(cand, cw, c, rr, lane, &s_cand);
     dsum = (s_below - static_cast<double>(rank - rr) * (tau - mu_d)) + s_cand;
   } else [[unlikely]] {
     // No spread in the moments: the noise-free step 0 of every obstacle (simulation/obstacles.py:63)
@@ -749,6 +776,7 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
     }
     if (wave != 0) {
       if (!PEER && wave == 1) write_mean_halfspace(rec, mux, muy, prm.rc, lane);
+      DRCVAR_STAMP_WAVE(2);  // diagnostic build: this wave's end
       return;
     }
     rch = prm.rc * norm_h(h0, h1);
@@ -761,6 +789,7 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
     finish_offsets<NW>(rec, prm, rch, h0, h1, tau, dsum, mux, muy, lane);
   if (status && lane == 0) status[u] = failure_status(false, prm);
   DRCVAR_STAMP(7);
+  DRCVAR_STAMP_WAVE(2);
 }
 
 

@@ -330,6 +330,39 @@ __device__ __forceinline__ void append_candidate(double* region, uint32_t& wbase
   wbase += static_cast<uint32_t>(__popcll(ballot));
 }
 
+// Wave 0 (all lanes active), a target bucket of c <= 64 / NW candidates: no wave holds more than
+// E = 64 / NW of them, so wave w appends its candidates to the segment cand[w * E + k] and all of
+// the unit's candidates lie in cand[0 .. 64), in rank_candidates' order (wave, then position)
+// with holes.  Lane l holds `mine` = cand[l] and `cnt` = wcount[l / E], and is a candidate iff
+// l % E < cnt — the caller issues both reads in one batch with its other post-barrier reads, so
+// nothing here computes a slot or waits on LDS again.  The candidates are visited in ascending
+// lane order, the visiting lane taken in scalar code from the ballot of the valid lanes: every
+// lane runs the same arithmetic on the same values in the same order as rank_candidates does on
+// the packed layout, and tau and s_cand come out bitwise the same.
+template <int NW>
+__device__ __forceinline__ double rank_candidates_express(double mine, uint32_t cnt, uint32_t rr,
+                                                          int lane, double* s_cand) {
+  constexpr int E = kWave / NW;
+  const bool valid = static_cast<uint32_t>(lane & (E - 1)) < cnt;
+  unsigned long long m = __ballot(valid);
+  uint32_t less = 0u, eq = 0u;
+  double sl = 0.0;
+  while (m != 0ull) {  // uniform
+    const int src = __builtin_ctzll(m);
+    m &= m - 1ull;
+    const double z = readlane_f64(mine, src);
+    const bool lt = z < mine;
+    less += lt ? 1u : 0u;
+    eq += (z == mine) ? 1u : 0u;
+    sl += lt ? z - mine : 0.0;
+  }
+  const bool found = valid && less <= rr && rr < less + eq;
+  const unsigned long long fb = __ballot(found);
+  const int src = __ffsll(static_cast<long long>(fb)) - 1;
+  *s_cand = readlane_f64(sl, src);
+  return readlane_f64(mine, src);
+}
+
 // Wave 0 (all lanes active): tau = the candidate of rank rr among the c <= kCap candidates held in
 // per-wave regions cand[w * kCap + i], i < wcount[w] (global order: wave, then position — fixed).
 // Candidates are pulled into registers (g = lane, lane + 64) and compared through readlane, so

@@ -29,13 +29,25 @@ for _ in range(30):
 torch.cuda.synchronize()
 lib = _native.lib()
 U = min(O * T, 16384)
-KS = 16 if os.environ.get("DRCVAR_STAMPS_WAVES") else 8  # a -DDRCVAR_STAMPS_WAVES build
+KS = 24 if os.environ.get("DRCVAR_STAMPS_WAVES") else 8  # a -DDRCVAR_STAMPS_WAVES build
 buf = (ctypes.c_ulonglong * (U * KS))()
 lib.drcvar_diag_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
 assert lib.drcvar_diag_stamps(ctypes.cast(buf, ctypes.c_void_p), U) == U
 st = np.frombuffer(buf, dtype=np.uint64).reshape(U, KS).astype(np.int64)
-if KS == 16:  # per-wave: loads summed (slots 8..11), reduction done before barrier 1 (12..15)
-    nw = 4
+if KS == 24:  # per-wave: loads summed (slots 8..11), reduction done before barrier 1 (12..15),
+    nw = 4    # the wave's end (16..19)
+    we = st[:, 16:16 + nw] - st[:, :1]
+    tot_w = we.max(1)
+    med_u, slow_u = int(np.argsort(tot_w)[len(tot_w) // 2]), int(np.argmax(tot_w))
+    print("  per wave, end of the wave in cycles from entry (median over units)",
+          np.median(we, 0).round().tolist(), " unit's last wave (median)", float(np.median(tot_w)))
+    print("  last wave to exit, share of units per wave",
+          np.bincount(we.argmax(1), minlength=nw).astype(float).__truediv__(len(we)).round(3).tolist(),
+          " wave 1's end - wave 0's end: median", float(np.median(we[:, 1] - we[:, 0])),
+          " p10", float(np.percentile(we[:, 1] - we[:, 0], 10)),
+          " p90", float(np.percentile(we[:, 1] - we[:, 0], 90)))
+    print(f"  median unit {med_u}: wave ends {we[med_u].tolist()}; slowest unit {slow_u}: wave ends"
+          f" {we[slow_u].tolist()}; barrier 3 passed (wave 0) {int(st[slow_u, 6] - st[slow_u, 0])}")
     ld = st[:, 8:8 + nw] - st[:, :1]
     rd = st[:, 12:12 + nw] - st[:, :1]
     print("  per wave, cycles from entry (median over units): loads summed",
