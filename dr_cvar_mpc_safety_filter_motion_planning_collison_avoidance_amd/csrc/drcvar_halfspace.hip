@@ -430,7 +430,9 @@ __device__ __forceinline__ void finish_offsets_peer(const PeerArgs& pa, unsigned
 // ---------------------------------------------------------------------------------------------
 //   PEER     the peer-push exchange form: records go to every rank's exchange region (PeerArgs)
 //            instead of `out`
-template <int BLOCK, int P, int LOG_NB, int LOAD, bool GIVEN_H, bool PEER>
+//   FULL     small plans (P <= 8) only: the host saw N > BLOCK * (P - 1), so rows 0 .. P-2 hold a
+//            sample in every thread and carry no `i < n` selects; the last row keeps them
+template <int BLOCK, int P, int LOG_NB, int LOAD, bool GIVEN_H, bool PEER, bool FULL>
 __global__ void __launch_bounds__(BLOCK)
 safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n,
                       int64_t s_obs, int64_t s_step, int64_t s_samp,
@@ -478,10 +480,11 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
   const int64_t off0 = static_cast<int64_t>(tid) * s_samp;
   const int64_t row_step = static_cast<int64_t>(BLOCK) * s_samp;
   const int64_t off_last = static_cast<int64_t>(n - 1) * s_samp;
+  // does this thread's slot of row j hold a sample?  (a constant for the rows known full)
+  const auto in_row = [&](int j) { return (FULL && j < P - 1) || tid + j * BLOCK < n; };
 #pragma unroll
   for (int j = 0; j < P; ++j) {
-    const int i = tid + j * BLOCK;
-    const int64_t off = i < n ? off0 + j * row_step : off_last;
+    const int64_t off = in_row(j) ? off0 + j * row_step : off_last;
     if constexpr (LOAD == kLoadNt) {  // streamed once: keep it out of L2 / MALL
       const dbl2 v = __builtin_nontemporal_load(reinterpret_cast<const dbl2*>(base + off));
       x[j] = v.x;
@@ -529,7 +532,7 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
   float mom0[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  // row 0, pivot-shifted: Sa Sb Saa Sbb Sab
 #pragma unroll
   for (int j = 0; j < P; ++j) {
-    const bool valid = tid + j * BLOCK < n;
+    const bool valid = in_row(j);
     const double a = valid ? x[j] : 0.0, b = valid ? y[j] : 0.0;
     mom[0] += a;
     mom[1] += b;
@@ -590,7 +593,7 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
   double d[P];
 #pragma unroll
   for (int j = 0; j < P; ++j)  // +inf padding: never below, inside or a candidate
-    d[j] = (tid + j * BLOCK < n) ? project(h0, h1, x[j], y[j]) : INFINITY;
+    d[j] = in_row(j) ? project(h0, h1, x[j], y[j]) : INFINITY;
   const double mu_d = h0 * mux + h1 * muy;
   double var_d;
   if constexpr (kPilot) {  // variance of the pilot's projections about the exact mean, in fp32
@@ -716,6 +719,7 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
     const uint32_t cx = wcount[lane / (kWave / NW)];
     const double mine = cand[lane];
     double s_below;
+    [[maybe_unused]] double tail_lane = 0.0;  // small plans: this lane's sum of the waves' tail partials
     if constexpr (kPilot) {
       double tl[NW];
 #pragma unroll
@@ -730,7 +734,7 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
       double t = tl[0];
 #pragma unroll
       for (int w = 1; w < NW; ++w) t += tl[w];
-      s_below = wave_reduce<OpAdd>(t);
+      tail_lane = t;  // reduced over the wave beside the ranking's first candidate, below
     } else {
       s_below = sum_partials<NW>(red_tail);
       lds_values_ready(cw);
@@ -739,7 +743,15 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
       rch = prm.rc * norm_h(h0, h1);  // R_c |h|: off the histogram's critical path
     }
     double s_cand;
-    if (express) [[likely]]
+    if constexpr (kPilot) {
+      // the tail's wave reduction in one basic block with the ranking's first candidate
+      if (express) [[likely]] {
+        tau = rank_candidates_express_tail<NW>(mine, cx, rr, lane, tail_lane, &s_below, &s_cand);
+      } else {
+        s_below = wave_reduce<OpAdd>(tail_lane);
+        tau = rank_candidates<NW>(cand, cw, c, rr, lane, &s_cand);
+      }
+    } else if (express) [[likely]]
       tau = rank_candidates_express<NW>(mine, cx, rr, lane, &s_cand);
     else
       tau = rank_candidates<NW>(cand, cw, c, rr, lane, &s_cand);
@@ -928,7 +940,7 @@ struct Launch {
 // larger batches are split into obstacle chunks on the host
 constexpr int64_t kMaxGridY = 65535;
 
-template <int BLOCK, int P, int LOG_NB, int LOAD, bool GIVEN_H, bool PEER>
+template <int BLOCK, int P, int LOG_NB, int LOAD, bool GIVEN_H, bool PEER, bool FULL>
 int launch_form(const Launch& L) {
   const int64_t n_obs = L.units / L.n_steps;
   const size_t dyn = 0;
@@ -936,7 +948,7 @@ int launch_form(const Launch& L) {
     const int64_t chunk = n_obs - o0 < kMaxGridY ? n_obs - o0 : kMaxGridY;
     PeerArgs pa = L.peer;
     pa.row_base += o0 * L.n_steps;
-    hipLaunchKernelGGL((safe_halfspace_kernel<BLOCK, P, LOG_NB, LOAD, GIVEN_H, PEER>),
+    hipLaunchKernelGGL((safe_halfspace_kernel<BLOCK, P, LOG_NB, LOAD, GIVEN_H, PEER, FULL>),
                        dim3(static_cast<unsigned>(L.n_steps), static_cast<unsigned>(chunk)),
                        dim3(BLOCK), dyn, L.stream, L.samples + o0 * L.s_obs, L.n_steps,
                        static_cast<int>(L.n), L.s_obs, L.s_step, L.s_samp,
@@ -947,6 +959,17 @@ int launch_form(const Launch& L) {
   return DRCVAR_OK;
 }
 
+// Small plans whose N fills every row but the last run the form without those rows' `i < n`
+// selects; any other N (an explicit geometry far larger than N included) the predicated form.
+template <int BLOCK, int P, int LOG_NB, int LOAD, bool GIVEN_H, bool PEER>
+int launch_rows(const Launch& L) {
+  if constexpr (P <= 8) {
+    if (L.n > static_cast<int64_t>(BLOCK) * (P - 1))
+      return launch_form<BLOCK, P, LOG_NB, LOAD, GIVEN_H, PEER, true>(L);
+  }
+  return launch_form<BLOCK, P, LOG_NB, LOAD, GIVEN_H, PEER, false>(L);
+}
+
 template <int BLOCK, int P, int LOG_NB, bool GIVEN_H, bool PEER>
 int launch_plan(Launch L, bool vec) {
   const int64_t sub = P <= 8 ? kWave : BLOCK;  // the window's subsample: pilot or row 0 (kernel)
@@ -955,10 +978,10 @@ int launch_plan(Launch L, bool vec) {
   // measured on C5 (2.05 GB): nontemporal 16-B loads 0.746 of HBM peak vs 0.715; on C3 (3.2 MB,
   // cache-resident across steps) they cost 3 %, so only launches larger than the MALL use them
   const bool nt = vec && L.units * L.n * 16 > kNtBytes;
-  if (nt) return launch_form<BLOCK, P, LOG_NB, kLoadNt, GIVEN_H, PEER>(L);
-  if (vec) return launch_form<BLOCK, P, LOG_NB, kLoadVec, GIVEN_H, PEER>(L);
+  if (nt) return launch_rows<BLOCK, P, LOG_NB, kLoadNt, GIVEN_H, PEER>(L);
+  if (vec) return launch_rows<BLOCK, P, LOG_NB, kLoadVec, GIVEN_H, PEER>(L);
   if constexpr (PEER) return DRCVAR_ERR_UNSUPPORTED;  // the peer form reads packed 16-B samples
-  else return launch_form<BLOCK, P, LOG_NB, kLoadPair, GIVEN_H, false>(L);
+  else return launch_rows<BLOCK, P, LOG_NB, kLoadPair, GIVEN_H, false>(L);
 }
 
 template <bool GIVEN_H>

@@ -363,6 +363,49 @@ __device__ __forceinline__ double rank_candidates_express(double mine, uint32_t 
   return readlane_f64(mine, src);
 }
 
+// rank_candidates_express with the tail's wave sum (*s_below = the sum of `tail` over the wave, by
+// wave_reduce's tree) in the same basic block as the ranking's first candidate: the bucket of this
+// path holds at least one, so the first visit is straight-line code whose readlanes and compares
+// fill the wait states of the reduction's DPP stages; the loop takes the remaining candidates (the
+// usual bucket has none: its exit is the fall-through).  The same operations on the same values in
+// the same order as rank_candidates_express: tau and s_cand are bitwise the same.
+template <int NW>
+__device__ __forceinline__ double rank_candidates_express_tail(double mine, uint32_t cnt,
+                                                               uint32_t rr, int lane, double tail,
+                                                               double* s_below, double* s_cand) {
+  constexpr int E = kWave / NW;
+  const bool valid = static_cast<uint32_t>(lane & (E - 1)) < cnt;
+  unsigned long long m = __ballot(valid);
+  uint32_t less = 0u, eq = 0u;
+  double sl = 0.0;
+  {  // the first candidate (m != 0 on this path)
+    const int src = __builtin_ctzll(m);
+    m &= m - 1ull;
+    const double z = readlane_f64(mine, src);
+    const bool lt = z < mine;
+    less += lt ? 1u : 0u;
+    eq += (z == mine) ? 1u : 0u;
+    sl += lt ? z - mine : 0.0;
+  }
+  *s_below = wave_reduce<OpAdd>(tail);
+  if (m != 0ull) [[unlikely]] {
+    do {  // uniform
+      const int src = __builtin_ctzll(m);
+      m &= m - 1ull;
+      const double z = readlane_f64(mine, src);
+      const bool lt = z < mine;
+      less += lt ? 1u : 0u;
+      eq += (z == mine) ? 1u : 0u;
+      sl += lt ? z - mine : 0.0;
+    } while (m != 0ull);
+  }
+  const bool found = valid && less <= rr && rr < less + eq;
+  const unsigned long long fb = __ballot(found);
+  const int src = __ffsll(static_cast<long long>(fb)) - 1;
+  *s_cand = readlane_f64(sl, src);
+  return readlane_f64(mine, src);
+}
+
 // Wave 0 (all lanes active): tau = the candidate of rank rr among the c <= kCap candidates held in
 // per-wave regions cand[w * kCap + i], i < wcount[w] (global order: wave, then position — fixed).
 // Candidates are pulled into registers (g = lane, lane + 64) and compared through readlane, so
