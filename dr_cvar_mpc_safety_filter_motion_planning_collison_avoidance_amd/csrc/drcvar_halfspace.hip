@@ -124,7 +124,9 @@ __device__ __forceinline__ void sum_stage(double* v, float* f) {
   for (int q = 0; q < KF; ++q) f[q] = f[q] + tf[q];
 }
 // (v, f: KD doubles and KF floats in registers — either count may be 0)
-template <int KD, int KF>
+// UNIFORM = false skips the last step, the move to SGPRs: the sums stay in VGPRs, where every lane
+// holds the same bits already.
+template <int KD, int KF, bool UNIFORM = true>
 __device__ __forceinline__ void wave_sum_multi(double* v, float* f) {
   sum_stage<kDppQuadXor1, KD, KF>(v, f);
   sum_stage<kDppQuadXor2, KD, KF>(v, f);
@@ -144,10 +146,12 @@ __device__ __forceinline__ void wave_sum_multi(double* v, float* f) {
     const auto b = __builtin_amdgcn_permlane32_swap(__float_as_int(f[q]), __float_as_int(f[q]), false, false);
     f[q] = __int_as_float(b[0]) + __int_as_float(b[1]);
   }
+  if constexpr (UNIFORM) {
 #pragma unroll
-  for (int q = 0; q < KD; ++q) v[q] = uniform_f64(v[q]);
+    for (int q = 0; q < KD; ++q) v[q] = uniform_f64(v[q]);
 #pragma unroll
-  for (int q = 0; q < KF; ++q) f[q] = uniform_f32(f[q]);
+    for (int q = 0; q < KF; ++q) f[q] = uniform_f32(f[q]);
+  }
 }
 
 // Workgroup sums of the load phase: KD fp64 values (the mean sums) and KF fp32 values (the
@@ -159,7 +163,12 @@ template <int NW, int KD, int KF, bool PILOT = false>
 __device__ __forceinline__ void block_sum_moments(double* v, float* f, double* slot_d, float* slot_f,
                                                   const double2* pilot = nullptr,
                                                   double2* pilot_v = nullptr) {
-  wave_sum_multi<KD, KF>(v, f);
+  // Small plans (PILOT) hand the sums over in VGPRs: lane 0 stores its wave's sums from the vector
+  // copy, and the workgroup's sums feed the mean and the direction — vector fp64 arithmetic —
+  // without a trip through SGPRs on either side of the barrier (those plans run at 59-79 VGPRs;
+  // the large ones, at 123-127, keep their uniform values in SGPRs).
+  constexpr bool kUniform = !PILOT;
+  wave_sum_multi<KD, KF, kUniform>(v, f);
   DRCVAR_STAMP_WAVE(1);  // diagnostic build: this wave's reduction done, before the barrier
   const int lane = threadIdx.x & (kWave - 1);
   if constexpr (NW > 1) {
@@ -173,9 +182,9 @@ __device__ __forceinline__ void block_sum_moments(double* v, float* f, double* s
     __syncthreads();
     if constexpr (PILOT) *pilot_v = pilot[lane];
 #pragma unroll
-    for (int q = 0; q < KD; ++q) v[q] = sum_partials<NW>(slot_d + q * NW);
+    for (int q = 0; q < KD; ++q) v[q] = sum_partials<NW, double, kUniform>(slot_d + q * NW);
 #pragma unroll
-    for (int q = 0; q < KF; ++q) f[q] = sum_partials<NW>(slot_f + q * NW);
+    for (int q = 0; q < KF; ++q) f[q] = sum_partials<NW, float, kUniform>(slot_f + q * NW);
   } else {
     if constexpr (PILOT) *pilot_v = pilot[lane];  // (one wave: each lane reads back its own store)
   }

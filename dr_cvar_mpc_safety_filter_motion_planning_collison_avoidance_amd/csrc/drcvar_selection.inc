@@ -124,7 +124,9 @@ __device__ __forceinline__ double wave_reduce(double v) {
 
 // Sum of NW per-wave partials p[0..NW) read by every thread (broadcast LDS reads), fixed
 // pairwise tree — cheaper than a second wave reduction for the small NW of the launch plans.
-template <int NW, class T>
+// UNIFORM = false leaves the sum in VGPRs (every lane holds the same bits): for a caller whose next
+// steps are vector arithmetic anyway and whose register budget has room.
+template <int NW, class T, bool UNIFORM = true>
 __device__ __forceinline__ T sum_partials(const T* p) {
   T v[NW];
 #pragma unroll
@@ -133,7 +135,9 @@ __device__ __forceinline__ T sum_partials(const T* p) {
   for (int stride = 1; stride < NW; stride *= 2)
 #pragma unroll
     for (int w = 0; w + stride < NW; w += 2 * stride) v[w] = v[w] + v[w + stride];
-  if constexpr (sizeof(T) == 8) {
+  if constexpr (!UNIFORM) {
+    return v[0];
+  } else if constexpr (sizeof(T) == 8) {
     return uniform_f64(v[0]);
   } else {
     return uniform_f32(v[0]);
@@ -253,33 +257,55 @@ __device__ __forceinline__ void load_bins(const uint32_t* hist, int lane, uint32
   for (int q = 0; q < B; ++q) h[q] = mine[q];
 }
 
+// One level of the owner lane's bin search: pre[0 .. 2 W] are non-decreasing prefix counts with
+// pre[0] <= rl < pre[2 W]; the half that holds the first prefix above rl is kept (a fresh array per
+// level, all indices constants: selects between registers), k gains W when it is the upper one.
+// At W = 1 the pair left is (lo, hi) = (pre[k], pre[k + 1]) of the first level's array.
+template <int W>
+__device__ __forceinline__ void halve_prefixes(const uint32_t (&pre)[2 * W + 1], uint32_t rl, int& k,
+                                               uint32_t& lo, uint32_t& hi) {
+  const bool up = pre[W] <= rl;
+  k += up ? W : 0;
+  if constexpr (W == 1) {
+    lo = up ? pre[1] : pre[0];
+    hi = up ? pre[2] : pre[1];
+  } else {
+    uint32_t half[W + 1];
+#pragma unroll
+    for (int i = 0; i <= W; ++i) half[i] = up ? pre[i + W] : pre[i];
+    halve_prefixes<W / 2>(half, rl, k, lo, hi);
+  }
+}
+
 // Any wave, its bins loaded (load_bins): the bin holding the sample of rank rr (0-based) and the
 // counts below / inside it.  Result is uniform across the wave.
 template <int NB>
 __device__ __forceinline__ ScanResult scan_loaded_bins(const uint32_t (&h)[NB / kWave], uint32_t rr,
                                                       int lane) {
   constexpr int B = NB / kWave;  // contiguous bins per lane
-  uint32_t s = 0;
+  static_assert(B >= 2 && (B & (B - 1)) == 0, "the owner search halves a power-of-two run of bins");
+  // pre[q] = samples of this lane's bins below bin q (pre[B] = the lane's total): independent of
+  // the wave scan, so the adds fill its DPP wait states
+  uint32_t pre[B + 1];
+  pre[0] = 0u;
 #pragma unroll
-  for (int q = 0; q < B; ++q) s += h[q];
+  for (int q = 0; q < B; ++q) pre[q + 1] = pre[q] + h[q];
+  const uint32_t s = pre[B];
   const uint32_t incl = wave_inclusive_scan(s, lane);
   const unsigned long long hit = __ballot(incl > rr);
   if (hit == 0ull) return ScanResult{0, 0u, 0u, false};
   const int owner = __ffsll(static_cast<long long>(hit)) - 1;  // uniform
-  // in the owner lane: first bin whose running count passes rr (branch-free over the B bins)
-  uint32_t cum = incl - s;
-  int bin = lane * B + B - 1;
-  uint32_t below = 0, cnt = 0;
-  bool done = false;
-#pragma unroll
-  for (int q = 0; q < B; ++q) {
-    const bool take = !done && cum + h[q] > rr;
-    bin = take ? lane * B + q : bin;
-    below = take ? cum : below;
-    cnt = take ? h[q] : cnt;
-    done = done || take;
-    cum += h[q];
-  }
+  // In the owner lane (the first with incl > rr) the samples below its bins number cum <= rr, and
+  // the target is its bin k = #{q >= 1 : pre[q] <= rl}, rl = rr - cum < s: pre[] is non-decreasing,
+  // so k comes from log2(B) compares, each keeping the half of pre[] that holds pre[k], pre[k + 1].
+  // The other lanes compute values nobody reads (rl wraps there).
+  const uint32_t cum = incl - s;
+  const uint32_t rl = rr - cum;
+  int k = 0;
+  uint32_t lo, hi;  // pre[k], pre[k + 1]
+  halve_prefixes<B / 2>(pre, rl, k, lo, hi);
+  const int bin = lane * B + k;
+  const uint32_t below = cum + lo, cnt = hi - lo;
   return ScanResult{__builtin_amdgcn_readlane(bin, owner),
                     static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(below), owner)),
                     static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cnt), owner)),
