@@ -21,7 +21,8 @@ SOURCES = [os.path.join(PKG_DIR, "csrc", "drcvar_halfspace.hip"),
            os.path.join(PKG_DIR, "csrc", "drcvar_sampling.hip"),
            os.path.join(PKG_DIR, "csrc", "drcvar_exchange.hip"),
            os.path.join(PKG_DIR, "csrc", "drcvar_clearance.hip"),
-           os.path.join(PKG_DIR, "csrc", "drcvar_sampled.hip")]
+           os.path.join(PKG_DIR, "csrc", "drcvar_sampled.hip"),
+           os.path.join(PKG_DIR, "csrc", "drcvar_step.hip")]
 INCLUDE_DIR = os.path.join(REPO_DIR, "include")
 HEADERS = [os.path.join(INCLUDE_DIR, h) for h in ("drcvar_halfspace.h", "drcvar_mpc.h",
                                                   "drcvar_sampling.h", "drcvar_exchange.h")]
@@ -68,6 +69,13 @@ class MpcOptions(ctypes.Structure):
                 ("reserved", ctypes.c_int32 * 2)]
 
 
+class StepState(ctypes.Structure):
+    """``drcvar_step_state`` (include/drcvar_sampling.h): the device-resident state of a
+    receding-horizon loop, 16 bytes — as a tensor, int64 ``[stream_offset, step]``."""
+
+    _fields_ = [("stream_offset", ctypes.c_uint64), ("step", ctypes.c_int64)]
+
+
 # peer-push exchange (include/drcvar_exchange.h)
 MAX_PEERS = 8
 PEER_HANDLE_BYTES = 64
@@ -96,11 +104,13 @@ EXPORTED_SYMBOLS = (
     "drcvar_mpc_launch_groups_ex",
     "drcvar_mpc_filter_f64",
     "drcvar_mpc_filter_f64_ex",
+    "drcvar_mpc_step_advance_f64",
     "drcvar_sample_trajectories_f64",
     "drcvar_sample_units_f64",
     "drcvar_min_clearance_f64",
     "drcvar_min_clearance_f64_ex",
     "drcvar_sampled_halfspaces_f64",
+    "drcvar_sampled_halfspaces_f64_dev",
     "drcvar_sampled_launch_plan",
     "drcvar_peer_region_doubles",
     "drcvar_peer_alloc",
@@ -337,6 +347,14 @@ def _bind(lib):
         ptr, i64, i64, i64, i64, i64, i64, i64, dbl, dbl, dbl, u64, u64, i32, ptr, i64,
         dbl, dbl, dbl, dbl, dbl, ptr, ptr, ptr, i64, i64, ptr]
     lib.drcvar_sampled_halfspaces_f64.restype = ctypes.c_int
+    lib.drcvar_sampled_halfspaces_f64_dev.argtypes = [
+        ptr, i64, i64, i64, i64, i64, i64, i64, i64, dbl, dbl, dbl, u64, ptr, i32, ptr, i64,
+        dbl, dbl, dbl, dbl, dbl, ptr, ptr, ptr]
+    lib.drcvar_sampled_halfspaces_f64_dev.restype = ctypes.c_int
+    lib.drcvar_mpc_step_advance_f64.argtypes = [
+        modelp, ptr, ptr, ptr, ptr, ptr, i64, ptr, i64, i64, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr,
+        ptr, ptr]
+    lib.drcvar_mpc_step_advance_f64.restype = ctypes.c_int
     lib.drcvar_sampled_launch_plan.argtypes = [i64, i32p, i32p]
     lib.drcvar_sampled_launch_plan.restype = ctypes.c_int
     peerp = ctypes.POINTER(PeerSet)

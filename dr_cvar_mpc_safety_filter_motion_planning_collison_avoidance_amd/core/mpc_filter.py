@@ -112,7 +112,7 @@ class MPCModel:
         self.host_blob = blob
         self.device = torch.device(device) if device is not None else risk_metrics.device()
         self.blob = torch.as_tensor(blob).to(self.device)
-        self.A, self.B = A, B
+        self.A, self.B, self.C = A, B, C
         self.nx, self.nu, self.horizon = nx, nu, int(horizon)
 
     def launch_groups(self, n_problems, n_obstacles, options=None):
@@ -137,13 +137,15 @@ def _check_dev(t, name, shape, device):
 def filter_batch(model: MPCModel, hs_h: torch.Tensor, hs_g: torch.Tensor, x0: torch.Tensor,
                  x_ref: torch.Tensor, u_fallback: torch.Tensor, max_iter: int = DEFAULT_MAX_ITER,
                  tol: float = DEFAULT_TOL, polish: bool = True,
-                 workspace: torch.Tensor | None = None, stream=None, options=None):
+                 workspace: torch.Tensor | None = None, stream=None, options=None, out=None):
     """Solve B safety-filter QPs on the device (one ``drcvar_mpc_filter_f64_ex`` launch).
 
     hs_h [B, O, K, 2] (any strides, last 1), hs_g [B, O, K]; x0 [B, nx]; x_ref [B, H+1, nx];
     u_fallback [B, H, nu].  Returns (x [B, H+1, nx], u [B, H, nu], info [B, 10]) device tensors
     (columns ``_native.MPC_INFO_*``); nothing is synchronised.  ``polish`` finishes each solve
     with the active-set polish (exact optimum when it succeeds).  ``options``: :func:`make_options`.
+    ``out=(x, u, info)``: preallocated contiguous outputs of exactly those shapes (a captured or
+    repeated launch writes the same buffers); the default allocates them.
     A clustered problem whose workgroups could not all stay resident, or disagreed, ends
     CLUSTER_TIMEOUT / CLUSTER_DIVERGED with the fallback rolled out; this function does not retry
     it — batch callers call :func:`retry_cluster_failures` on the result themselves (the
@@ -161,9 +163,17 @@ def filter_batch(model: MPCModel, hs_h: torch.Tensor, hs_g: torch.Tensor, x0: to
     _check_dev(x0, "x0", (B, nx), dev)
     _check_dev(x_ref, "x_ref", (B, H + 1, nx), dev)
     _check_dev(u_fallback, "u_fallback", (B, H, nu), dev)
-    x = torch.empty((B, H + 1, nx), dtype=torch.float64, device=dev)
-    u = torch.empty((B, H, nu), dtype=torch.float64, device=dev)
-    info = torch.empty((B, _native.MPC_INFO_WIDTH), dtype=torch.float64, device=dev)
+    if out is None:
+        x = torch.empty((B, H + 1, nx), dtype=torch.float64, device=dev)
+        u = torch.empty((B, H, nu), dtype=torch.float64, device=dev)
+        info = torch.empty((B, _native.MPC_INFO_WIDTH), dtype=torch.float64, device=dev)
+    else:
+        x, u, info = out
+        for t, name, shape in ((x, "out x", (B, H + 1, nx)), (u, "out u", (B, H, nu)),
+                               (info, "out info", (B, _native.MPC_INFO_WIDTH))):
+            _check_dev(t, name, shape, dev)
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
     need = model.workspace_doubles(B, O)
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(max(need, 1), dtype=torch.float64, device=dev)

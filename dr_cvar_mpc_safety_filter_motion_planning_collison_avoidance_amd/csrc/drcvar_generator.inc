@@ -1,6 +1,7 @@
 // drcvar_generator.inc — the obstacle-sample generator's device arithmetic (Philox4x32-10,
 // Box-Muller from 32-bit uniforms, the LDS tables, the pair of samples of one Philox call) and the
-// host-made uniforms it takes (PhiloxUniform, LogScale), for the three kernels that draw: the
+// uniforms it takes (PhiloxUniform, LogScale; host-made, PhiloxUniform also in scalar device
+// code), for the three kernels that draw: the
 // sampler (drcvar_sampling.hip), the clearance evaluation (drcvar_clearance.hip) and the sampled
 // halfspaces (drcvar_sampled.hip).  Included inside each file's anonymous namespace, after
 // <cstdint> and <cstring>.  The host mirror is oracle/philox_sampler.py.
@@ -27,7 +28,10 @@ struct PhiloxUniform {
 constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
 constexpr uint64_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
 
-inline PhiloxUniform make_philox_uniform(uint32_t s0, uint32_t s1, uint32_t k0, uint32_t k1) {
+// (Host and device: the device-state form of the sampled halfspaces makes it in the kernel, in
+// scalar code, from stream words it loads; every other kernel takes the host-made struct.)
+__host__ __device__ inline PhiloxUniform make_philox_uniform(uint32_t s0, uint32_t s1, uint32_t k0,
+                                                             uint32_t k1) {
   const uint64_t q1 = kPhiloxM1 * s0;
   PhiloxUniform p{};
   p.a1 = static_cast<uint32_t>(q1 >> 32) ^ k0;

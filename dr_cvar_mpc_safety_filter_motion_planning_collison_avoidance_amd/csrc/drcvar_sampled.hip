@@ -26,6 +26,11 @@
 //
 // samples_out (optional): the kernel also stores the samples it drew; the record is the same bits.
 //
+// Two entries, one kernel template: drcvar_sampled_halfspaces_f64 freezes the stream offset and the
+// window in its arguments; drcvar_sampled_halfspaces_f64_dev (DEV below) reads the offset and the
+// window's first path row from a 16-byte state in device memory, so that a receding-horizon loop
+// can be replayed from one graph with a fresh draw per step (simulation/closed_loop.py).
+//
 // The draw is the sampler's (drcvar_generator.inc) and the selection the stored form's
 // (drcvar_selection.inc); the direction alone differs on purpose, by one more Newton step of the
 // reciprocal square root (rsqrt_nr2).
@@ -34,6 +39,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 #include "drcvar_sampling.h"
 
@@ -181,14 +187,38 @@ __device__ __forceinline__ void select_from_registers(const double (&d)[Q], uint
 //   PP       Philox pairs per thread (N <= 2 BLOCK PP)
 //   LOG_NB   log2 of the histogram bins
 //   ISO      the sampler's isotropic LogScale form
+//   DEV      the device-state form (below)
 // Blocks of 512 threads are held to 128 VGPRs (four waves per SIMD): two workgroups share a CU,
 // so one unit's draw (VALU) overlaps the other's selection (barriers, LDS, one ranking wave).
+//
+// The device-state form (DEV, drcvar_sampled_halfspaces_f64_dev): the stream words and the
+// window's first path row come from `dev.state` in device memory, so a captured launch follows
+// them from replay to replay.  Window unit (o, t) takes path row c(step + t), c = clamp to
+// [0, path_last]; the Philox counter stays window-relative, so the launch is the base form on the
+// gathered window.  One template, one body: without DEV it compiles to the instructions the
+// kernel had before the flag existed (hipcc -S, every plan, both ISO forms).
+//
+// `state` is one uniform 16-byte load (both words of a const __restrict__ kernel argument, read
+// before any store: scalar memory).  Its writer is an earlier kernel or copy on the same stream
+// (the advance kernel's plain vector stores, drcvar_step.hip): a kernel's stores are written back
+// to L2 when it ends, and the scalar and vector L1 caches are invalidated before the next dispatch
+// of the in-order queue starts, so the scalar load reads L2's value.  Nothing inside one launch
+// writes `state`, so no finer ordering is needed.  PhiloxUniform is then made here, in scalar code
+// (one 32 x 32 -> 64 product, three xors), by the make_philox_uniform the host uses; a.pu arrives
+// with the key.
 // ---------------------------------------------------------------------------------------------
-template <int BLOCK, int PP, int LOG_NB, bool ISO>
+struct NoState {};
+struct DevState {
+  const drcvar_step_state* __restrict__ state;
+  int64_t path_last;
+};
+
+template <int BLOCK, int PP, int LOG_NB, bool ISO, bool DEV = false>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BLOCK >= 512 ? 4 : 1)))
 sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __restrict__ ego,
                          DrawArgs a, Params prm, double* __restrict__ out,
-                         int32_t* __restrict__ status, double* __restrict__ samples_out) {
+                         int32_t* __restrict__ status, double* __restrict__ samples_out,
+                         std::conditional_t<DEV, DevState, NoState> dev) {
   constexpr int NW = BLOCK / kWave;
   constexpr int NB = 1 << LOG_NB;
   constexpr int Q = 2 * PP;  // sample slots per thread: 2 j the pair's first, 2 j + 1 its second
@@ -208,9 +238,25 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
   const int64_t row = blockIdx.x;                              // the unit's row of out / status
   const int64_t u = a.u0 + row;
   const int64_t o = u / a.T, t = u - o * a.T;
-  const double* nom = nominal + o * a.nom_so + t * a.nom_st;
+  int64_t r = t;  // the unit's row of nominal[o] and of ego
+  if constexpr (DEV) {
+    const uint64_t words = dev.state->stream_offset;
+    const int64_t step = dev.state->step;
+    a.pu = make_philox_uniform(static_cast<uint32_t>(words), static_cast<uint32_t>(words >> 32),
+                               a.pu.k0, a.pu.k1);
+    // each word pinned as one scalar value: seen through, the xors that made them are
+    // re-associated into the rounds' per-lane xors (two more v_xor per Philox call)
+    a.pu.a1 = __builtin_amdgcn_readfirstlane(a.pu.a1);
+    a.pu.b1 = __builtin_amdgcn_readfirstlane(a.pu.b1);
+    a.pu.c1 = __builtin_amdgcn_readfirstlane(a.pu.c1);
+    a.pu.b2 = __builtin_amdgcn_readfirstlane(a.pu.b2);
+    // any step: held to [-T, path_last] first, so step + t cannot overflow and clamps the same
+    const int64_t s = step < -a.T ? -a.T : (step > dev.path_last ? dev.path_last : step);
+    r = s + t < 0 ? 0 : (s + t > dev.path_last ? dev.path_last : s + t);
+  }
+  const double* nom = nominal + o * a.nom_so + r * a.nom_st;
   const double nx = nom[0], ny = nom[1];
-  const double* ep = ego + t * a.ego_st;
+  const double* ep = ego + r * a.ego_st;
   const double e0 = ep[0], e1 = ep[1];
   const int n = a.n;
   const int pairs = (n + 1) >> 1;  // Philox calls per unit
@@ -422,21 +468,108 @@ struct Launch {
   double* out;
   int32_t* status;
   double* samples_out;
+  const drcvar_step_state* state;  // non-null: the device-state form, rows clamped to path_last
+  int64_t path_last;
   int64_t count;
   bool iso;
   hipStream_t stream;
 };
 
+template <int BLOCK, int PP, int LOG_NB, bool ISO>
+void launch_form(const Launch& L) {
+  const dim3 grid(static_cast<unsigned>(L.count)), block(BLOCK);
+  if (L.state)
+    hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true>), grid, block, 0,
+                       L.stream, L.nominal, L.ego, L.a, L.prm, L.out, L.status, nullptr,
+                       DevState{L.state, L.path_last});
+  else
+    hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, false>), grid, block, 0,
+                       L.stream, L.nominal, L.ego, L.a, L.prm, L.out, L.status, L.samples_out,
+                       NoState{});
+}
+
 template <int BLOCK, int PP, int LOG_NB>
 void launch_plan(Launch L) {
   L.prm.hist_scale = static_cast<double>(1 << LOG_NB) / (2.0 * L.prm.window_sd);
-  const dim3 grid(static_cast<unsigned>(L.count)), block(BLOCK);
   if (L.iso)
-    hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, true>), grid, block, 0, L.stream,
-                       L.nominal, L.ego, L.a, L.prm, L.out, L.status, L.samples_out);
+    launch_form<BLOCK, PP, LOG_NB, true>(L);
   else
-    hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, false>), grid, block, 0, L.stream,
-                       L.nominal, L.ego, L.a, L.prm, L.out, L.status, L.samples_out);
+    launch_form<BLOCK, PP, LOG_NB, false>(L);
+}
+
+// Both entries: the host checks, the launch-uniform arguments and the plan's launch.  `state`
+// non-null selects the device-state form (n_steps is then the window length, path_steps the rows
+// of nominal and ego; stream_offset is unused, the kernel loads it).
+int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_steps, int64_t nom_so,
+                       int64_t nom_st, int64_t unit_begin, int64_t unit_count, int64_t n_samples,
+                       double l00, double l10, double l11, uint64_t seed, uint64_t stream_offset,
+                       const drcvar_step_state* state, bool dev, int64_t path_steps,
+                       int32_t zero_first_step, const double* ego, int64_t ego_stride,
+                       double robot_radius, double obstacle_radius, double alpha, double delta,
+                       double epsilon, double* out, int32_t* status, double* samples_out, int64_t su,
+                       int64_t sn, void* stream) {
+  if (n_obstacles < 0 || n_steps < 0 || n_samples < 0 || unit_begin < 0 || unit_count < 0)
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (dev && path_steps < 1) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (!(l00 == l00) || !(l10 == l10) || !(l11 == l11)) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (!params_ok(robot_radius, obstacle_radius, alpha, delta, epsilon))
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  // the sampler's grid limits, and the register plans' sample count
+  if (n_obstacles > (int64_t{1} << 40) || n_steps > (int64_t{1} << 40) ||
+      n_obstacles * n_steps > (int64_t{1} << 40) || n_samples > DRCVAR_MAX_SAMPLES)
+    return DRCVAR_ERR_UNSUPPORTED;
+  const int64_t units = n_obstacles * n_steps;
+  if (unit_begin > units || unit_count > units - unit_begin) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (unit_count == 0 || n_samples == 0) return DRCVAR_OK;
+  if (!nominal || !ego || !out) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (dev && (!state || reinterpret_cast<uintptr_t>(state) % 16 != 0))
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (unit_count > 0x7fffffffLL) return DRCVAR_ERR_UNSUPPORTED;  // one workgroup per unit: grid x
+  Launch L{};
+  L.nominal = nominal;
+  L.ego = ego;
+  L.a.T = n_steps;
+  L.a.nom_so = nom_so;
+  L.a.nom_st = nom_st;
+  L.a.ego_st = ego_stride;
+  L.a.u0 = unit_begin;
+  L.a.su = su;
+  L.a.sn = sn;
+  L.a.n = static_cast<int>(n_samples);
+  L.a.zero_first = zero_first_step != 0;
+  L.a.l00 = l00;
+  L.a.l10 = l10;
+  L.a.l11 = l11;
+  // (the device-state form replaces all but the key words in the kernel)
+  L.a.pu = make_philox_uniform(static_cast<uint32_t>(stream_offset),
+                               static_cast<uint32_t>(stream_offset >> 32),
+                               static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
+  // the sampler's test for its isotropic form (launch_samples): the draws are the same bits only
+  // if this kernel takes that form exactly when the sampler does
+  const double lam = l00 * l00;
+  L.iso = l10 == 0.0 && l00 == l11 && l00 > 0.0 && std::isfinite(l00) && lam >= 0x1.0p-200 &&
+          lam <= 0x1.0p200;
+  L.a.lg = make_log_scale(L.iso ? lam : 1.0);
+  L.prm = make_params(robot_radius, obstacle_radius, alpha, delta, epsilon, n_samples);
+  L.out = out;
+  L.status = status;
+  L.samples_out = samples_out;
+  L.state = dev ? state : nullptr;
+  L.path_last = path_steps - 1;
+  L.count = unit_count;
+  L.stream = static_cast<hipStream_t>(stream);
+  (void)hipGetLastError();  // clear stale errors from unrelated work
+  switch (pick_plan(n_samples)) {
+    case 0: launch_plan<64, 1, 7>(L); break;
+    case 1: launch_plan<256, 1, 8>(L); break;
+    case 2: launch_plan<512, 1, 9>(L); break;
+    case 3: launch_plan<512, 2, 10>(L); break;
+    case 4: launch_plan<512, 4, 10>(L); break;
+    case 5: launch_plan<512, 8, 10>(L); break;
+    case 6: launch_plan<1024, 8, 10>(L); break;
+    default: return DRCVAR_ERR_UNSUPPORTED;
+  }
+  return hipGetLastError() == hipSuccess ? DRCVAR_OK : DRCVAR_ERR_LAUNCH;
 }
 
 }  // namespace
@@ -458,60 +591,21 @@ extern "C" int drcvar_sampled_halfspaces_f64(
     int64_t ego_stride, double robot_radius, double obstacle_radius, double alpha, double delta,
     double epsilon, double* out, int32_t* status, double* samples_out, int64_t su, int64_t sn,
     void* stream) {
-  if (n_obstacles < 0 || n_steps < 0 || n_samples < 0 || unit_begin < 0 || unit_count < 0)
-    return DRCVAR_ERR_INVALID_ARGUMENT;
-  if (!(l00 == l00) || !(l10 == l10) || !(l11 == l11)) return DRCVAR_ERR_INVALID_ARGUMENT;
-  if (!params_ok(robot_radius, obstacle_radius, alpha, delta, epsilon))
-    return DRCVAR_ERR_INVALID_ARGUMENT;
-  // the sampler's grid limits, and the register plans' sample count
-  if (n_obstacles > (int64_t{1} << 40) || n_steps > (int64_t{1} << 40) ||
-      n_obstacles * n_steps > (int64_t{1} << 40) || n_samples > DRCVAR_MAX_SAMPLES)
-    return DRCVAR_ERR_UNSUPPORTED;
-  const int64_t units = n_obstacles * n_steps;
-  if (unit_begin > units || unit_count > units - unit_begin) return DRCVAR_ERR_INVALID_ARGUMENT;
-  if (unit_count == 0 || n_samples == 0) return DRCVAR_OK;
-  if (!nominal || !ego || !out) return DRCVAR_ERR_INVALID_ARGUMENT;
-  if (unit_count > 0x7fffffffLL) return DRCVAR_ERR_UNSUPPORTED;  // one workgroup per unit: grid x
-  Launch L{};
-  L.nominal = nominal;
-  L.ego = ego;
-  L.a.T = n_steps;
-  L.a.nom_so = nom_so;
-  L.a.nom_st = nom_st;
-  L.a.ego_st = ego_stride;
-  L.a.u0 = unit_begin;
-  L.a.su = su;
-  L.a.sn = sn;
-  L.a.n = static_cast<int>(n_samples);
-  L.a.zero_first = zero_first_step != 0;
-  L.a.l00 = l00;
-  L.a.l10 = l10;
-  L.a.l11 = l11;
-  L.a.pu = make_philox_uniform(static_cast<uint32_t>(stream_offset),
-                               static_cast<uint32_t>(stream_offset >> 32),
-                               static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
-  // the sampler's test for its isotropic form (launch_samples): the draws are the same bits only
-  // if this kernel takes that form exactly when the sampler does
-  const double lam = l00 * l00;
-  L.iso = l10 == 0.0 && l00 == l11 && l00 > 0.0 && std::isfinite(l00) && lam >= 0x1.0p-200 &&
-          lam <= 0x1.0p200;
-  L.a.lg = make_log_scale(L.iso ? lam : 1.0);
-  L.prm = make_params(robot_radius, obstacle_radius, alpha, delta, epsilon, n_samples);
-  L.out = out;
-  L.status = status;
-  L.samples_out = samples_out;
-  L.count = unit_count;
-  L.stream = static_cast<hipStream_t>(stream);
-  (void)hipGetLastError();  // clear stale errors from unrelated work
-  switch (pick_plan(n_samples)) {
-    case 0: launch_plan<64, 1, 7>(L); break;
-    case 1: launch_plan<256, 1, 8>(L); break;
-    case 2: launch_plan<512, 1, 9>(L); break;
-    case 3: launch_plan<512, 2, 10>(L); break;
-    case 4: launch_plan<512, 4, 10>(L); break;
-    case 5: launch_plan<512, 8, 10>(L); break;
-    case 6: launch_plan<1024, 8, 10>(L); break;
-    default: return DRCVAR_ERR_UNSUPPORTED;
-  }
-  return hipGetLastError() == hipSuccess ? DRCVAR_OK : DRCVAR_ERR_LAUNCH;
+  return sampled_halfspaces(nominal, n_obstacles, n_steps, nom_so, nom_st, unit_begin, unit_count,
+                            n_samples, l00, l10, l11, seed, stream_offset, nullptr, false, 0,
+                            zero_first_step, ego, ego_stride, robot_radius, obstacle_radius, alpha,
+                            delta, epsilon, out, status, samples_out, su, sn, stream);
+}
+
+extern "C" int drcvar_sampled_halfspaces_f64_dev(
+    const double* nominal_path, int64_t n_obstacles, int64_t path_steps, int64_t nom_so,
+    int64_t nom_st, int64_t n_steps, int64_t unit_begin, int64_t unit_count, int64_t n_samples,
+    double l00, double l10, double l11, uint64_t seed, const drcvar_step_state* state,
+    int32_t zero_first_step, const double* ego_path, int64_t ego_stride, double robot_radius,
+    double obstacle_radius, double alpha, double delta, double epsilon, double* out,
+    int32_t* status, void* stream) {
+  return sampled_halfspaces(nominal_path, n_obstacles, n_steps, nom_so, nom_st, unit_begin,
+                            unit_count, n_samples, l00, l10, l11, seed, 0, state, true, path_steps,
+                            zero_first_step, ego_path, ego_stride, robot_radius, obstacle_radius,
+                            alpha, delta, epsilon, out, status, nullptr, 0, 0, stream);
 }

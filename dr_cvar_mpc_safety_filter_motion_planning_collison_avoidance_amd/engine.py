@@ -10,6 +10,9 @@ These are the batched calls everything else is built on:
 * :func:`sampled_halfspaces` — ``drcvar_sampled_halfspaces_f64``: the same records straight from
   the nominal paths ``[O, T, 2]``, each unit's samples drawn inside the kernel and never stored
   (``simulation/obstacles.py:43-77`` + ``core/halfspaces.py:196-248`` in one launch).
+* :func:`sampled_halfspaces_dev` — ``drcvar_sampled_halfspaces_f64_dev``: the same launch with the
+  window start and the stream offset read from a device-resident state, for a receding-horizon
+  loop replayed from one graph (``simulation/closed_loop.py``).
 
 All enqueue one kernel on the current HIP stream and return without synchronising.  Inputs must
 be float64 CUDA tensors whose two coordinates are adjacent (last stride 1); any other strides are
@@ -283,6 +286,107 @@ def sampled_halfspaces(nominal: torch.Tensor, ego: torch.Tensor, n_samples: int,
     between the two forms, the caller chooses.
     """
     launch, out = prepare_sampled_halfspaces(nominal, ego, n_samples, params, **kwargs)
+    if out.numel() > 0:
+        launch()
+    return out
+
+
+def check_step_state(state, device: torch.device) -> None:
+    """``state`` of the device-state entries: an int64 device tensor ``[stream_offset, step]``
+    (``_native.StepState``; the offset as its two's-complement bit pattern), 16-byte aligned."""
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int64:
+        raise ValueError("state must be an int64 tensor [stream_offset, step]")
+    if state.device != device:
+        raise ValueError(f"state must live on {device}, got {state.device}")
+    if tuple(state.shape) != (2,) or not state.is_contiguous():
+        raise ValueError(f"state must be a contiguous tensor of 2 elements, got {tuple(state.shape)}")
+    if state.data_ptr() % 16 != 0:
+        raise ValueError("state must be 16-byte aligned")
+
+
+def check_path(t, name: str, shape, device=None) -> None:
+    """A whole path of the device-state entries: a float64 tensor of ``shape`` (None = any size)
+    with a contiguous last dimension, on the GPU (``device``, when given).  Dtype and shape are
+    checked before the device."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+        raise ValueError(f"{name} must be a float64 tensor")
+    if t.dim() != len(shape) or any(w is not None and w != g for w, g in zip(shape, t.shape)):
+        raise ValueError(f"{name} must have shape {list(shape)}, got {tuple(t.shape)}")
+    if t.shape[0] < 1 or (t.dim() == 3 and t.shape[1] < 1):
+        raise ValueError(f"{name}: a path needs at least one row")
+    if t.stride(-1) != 1:
+        raise ValueError(f"{name}: the last dimension must be contiguous")
+    if t.device.type != "cuda":
+        raise ValueError(f"{name} must live on the GPU (HIP device tensor); the engine has no CPU path")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name} must live on {device}, got {t.device}")
+
+
+def prepare_sampled_halfspaces_dev(nominal_path: torch.Tensor, ego_path: torch.Tensor, n_steps: int,
+                                   n_samples: int, params: RiskParams, state: torch.Tensor,
+                                   noise_cov=DEFAULT_NOISE_COV, seed: int = 0,
+                                   zero_first_step: bool = True, unit_begin: int = 0,
+                                   unit_count: int | None = None, out: torch.Tensor | None = None,
+                                   status: torch.Tensor | None = None, stream=None,
+                                   chol=None) -> tuple[PreparedLaunch, torch.Tensor]:
+    """Freeze one ``drcvar_sampled_halfspaces_f64_dev`` call: :func:`prepare_sampled_halfspaces` on
+    the window of ``n_steps`` rows that starts at ``state[1]``, drawn with the stream offset
+    ``state[0]`` — both read from device memory when the kernel runs, so a graph that captured
+    the launch follows ``state`` from replay to replay.
+
+    nominal_path ``[O, P, 2]`` and ego_path ``[P, 2]`` float64 device tensors with adjacent
+    coordinates (whole paths, ``P >= 1``); window row ``t`` is path row ``min(max(step + t, 0),
+    P - 1)``.  ``state``: :func:`check_step_state`.  The records and status words are bit for bit
+    those of :func:`sampled_halfspaces` on the gathered window with that offset; the other arguments
+    are its own (``out`` is ``[O, n_steps, 8]``, or ``[unit_count, 8]`` for a unit window)."""
+    params.validate()
+    if not isinstance(nominal_path, torch.Tensor) or nominal_path.dim() != 3 or nominal_path.shape[0] < 1:
+        raise ValueError("nominal_path must be float64 [O, P, 2] with O, P >= 1")
+    check_path(nominal_path, "nominal_path", (None, None, 2))
+    dev = nominal_path.device
+    O, P, _ = nominal_path.shape
+    check_path(ego_path, "ego_path", (P, 2), dev)
+    check_step_state(state, dev)
+    T, n = int(n_steps), int(n_samples)
+    if T < 0:
+        raise ValueError(f"n_steps={T} must not be negative")
+    if n < 1 or n > _native.MAX_SAMPLES:
+        raise ValueError(f"n_samples={n} outside 1..{_native.MAX_SAMPLES}")
+    whole = unit_count is None
+    u0 = int(unit_begin)
+    count = O * T - u0 if whole else int(unit_count)
+    if u0 < 0 or count < 0 or u0 + count > O * T:
+        raise ValueError(f"unit range [{u0}, {u0 + count}) outside the {O} x {T} grid")
+    whole = whole and u0 == 0
+    shape = (O, T, OUT_WIDTH) if whole else (count, OUT_WIDTH)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=dev)
+    else:
+        _check_out(out, shape, dev, "[O, T, 8]" if whole else "[units, 8]")
+    if status is not None:
+        _check_status(status, count, dev)
+    l00, l10, l11 = _noise_factor(noise_cov, chol)
+    args = (ctypes.c_void_p(nominal_path.data_ptr()), O, P, nominal_path.stride(0),
+            nominal_path.stride(1), T, u0, count, n, l00, l10, l11,
+            ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), ctypes.c_void_p(state.data_ptr()),
+            ctypes.c_int32(1 if zero_first_step else 0),
+            ctypes.c_void_p(ego_path.data_ptr()), ego_path.stride(0),
+            params.robot_radius, params.obstacle_radius, params.alpha, params.delta, params.epsilon,
+            ctypes.c_void_p(out.data_ptr()),
+            ctypes.c_void_p(status.data_ptr() if status is not None else None),
+            ctypes.c_void_p(_stream_handle(dev, stream)))
+    launch = PreparedLaunch(_native.lib().drcvar_sampled_halfspaces_f64_dev, args,
+                            (nominal_path, ego_path, state, out, status))
+    return launch, out
+
+
+def sampled_halfspaces_dev(nominal_path: torch.Tensor, ego_path: torch.Tensor, n_steps: int,
+                           n_samples: int, params: RiskParams, state: torch.Tensor,
+                           **kwargs) -> torch.Tensor:
+    """One ``drcvar_sampled_halfspaces_f64_dev`` launch (arguments:
+    :func:`prepare_sampled_halfspaces_dev`): the halfspaces of the window that ``state`` names."""
+    launch, out = prepare_sampled_halfspaces_dev(nominal_path, ego_path, n_steps, n_samples, params,
+                                                 state, **kwargs)
     if out.numel() > 0:
         launch()
     return out

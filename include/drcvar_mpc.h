@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "drcvar_halfspace.h"
+#include "drcvar_sampling.h" /* drcvar_step_state */
 
 #ifdef __cplusplus
 extern "C" {
@@ -189,6 +190,51 @@ int drcvar_mpc_filter_f64_ex(const drcvar_mpc_model* model, const double* blob, 
                              double* u_out, double* info_out, double* workspace,
                              int64_t workspace_doubles, const drcvar_mpc_options* options,
                              void* stream);
+
+/*
+ * Close one control step of ONE problem's receding-horizon loop (csrc/drcvar_step.hip): one small
+ * launch (a single workgroup) that runs after drcvar_mpc_filter_f64[_ex] on the same stream, takes
+ * the step's answer and prepares every device buffer the next step's launches read, so that the
+ * loop sampled halfspaces (drcvar_sampled_halfspaces_f64_dev) -> solver -> advance can be captured
+ * once and replayed with no host work between steps.  The reference's loop is the caller of
+ * filter_trajectory once per control step (core/mpc_filter.py:40-178 with _fallback, :180-219).
+ *
+ * With s = state->step, i = s - step_begin (step_begin: the loop's first step, a host argument, so
+ * frozen in a graph), s' = s + 1, H = model->horizon and c(r) = min(max(r, 0), path_steps - 1), in
+ * this order:
+ *   1. next state     x_next = x_out[1, :] (+ disturbance[i, :] when disturbance is not NULL and
+ *                     0 <= i < log_rows)
+ *   2. log            for 0 <= i < log_rows only: x_log[i + 1, :] = x_next, u_log[i, :] = u_out[0, :],
+ *                     info_log[i, :] = info[0 .. DRCVAR_MPC_INFO_WIDTH)
+ *   3. fallback memory  info[STATUS] OPTIMAL or OPTIMAL_INACCURATE: last_u = u_out, *have_last = 1;
+ *                     otherwise both stay (last_optimal_u is set only on a solved call, :154-157,
+ *                     and a stale one is shifted again on the next failure)
+ *   4. next x0        x0 = x_next
+ *   5. next reference window   x_ref_win[k, :] = x_ref_path[c(s' + k), :], k = 0 .. H
+ *   6. next fallback inputs    with *have_last: u_fallback[k] = last_u[k + 1] for k < H - 1 and
+ *                     u_fallback[H - 1] = u_ref_path[c(s' + H - 1)] (_fallback's shift, :197-207);
+ *                     without: u_fallback[k] = u_ref_path[c(s' + k)]
+ *   7. state          state->step = s', state->stream_offset += 1 (wrapping at 2^64)
+ * No value of `state` causes an out-of-range access (s' past the paths' end holds their last row).
+ *
+ *   x_out [H+1, nx], u_out [H, nu], info [DRCVAR_MPC_INFO_WIDTH]   the solver's outputs (dense)
+ *   x_ref_path [path_steps, nx], u_ref_path [path_steps, nu]       read-only paths (dense)
+ *   disturbance [log_rows, nx] or NULL                             read-only
+ *   x_log [log_rows + 1, nx], u_log [log_rows, nu], info_log [log_rows, DRCVAR_MPC_INFO_WIDTH]
+ *   x0 [nx], x_ref_win [H+1, nx], u_fallback [H, nu], last_u [H, nu], have_last [1], state
+ *                     fixed device buffers (dense) that the captured solver / halfspace launches
+ *                     read; none may overlap another or an input.
+ * Host checks: a null pointer (disturbance excepted), a `state` not 16-byte aligned, a negative
+ * log_rows, path_steps < 1, or horizon / n_states / n_inputs outside 1 .. DRCVAR_MPC_MAX_*:
+ * DRCVAR_ERR_INVALID_ARGUMENT.  Asynchronous on `stream`, no allocation, no synchronisation.
+ */
+int drcvar_mpc_step_advance_f64(const drcvar_mpc_model* model, const double* x_out,
+                                const double* u_out, const double* info, const double* x_ref_path,
+                                const double* u_ref_path, int64_t path_steps,
+                                const double* disturbance, int64_t step_begin, int64_t log_rows,
+                                double* x_log, double* u_log, double* info_log, double* x0,
+                                double* x_ref_win, double* u_fallback, double* last_u,
+                                int32_t* have_last, drcvar_step_state* state, void* stream);
 
 #ifdef __cplusplus
 }

@@ -162,7 +162,8 @@ int drcvar_min_clearance_f64_ex(const double* ego, int64_t n_traj, int64_t ego_s
  * Unit-level exits (sentinels + status) as in drcvar_safe_halfspaces_f64_v2: alpha N > N,
  * epsilon < 0, a non-finite sum (here from a non-finite nominal position or factor).
  * Asynchronous on `stream`, no allocation, no synchronisation: the call can be captured in a graph
- * (a captured launch replays the same draw).
+ * (a captured launch replays the same draw; drcvar_sampled_halfspaces_f64_dev below reads the
+ * stream offset from device memory instead, for a fresh draw per replay).
  */
 int drcvar_sampled_halfspaces_f64(
     const double* nominal, int64_t n_obstacles, int64_t n_steps, int64_t nom_so, int64_t nom_st,
@@ -174,6 +175,49 @@ int drcvar_sampled_halfspaces_f64(
     double* out, int32_t* status,
     double* samples_out, int64_t su, int64_t sn,
     void* stream);
+
+/* device-resident, 16-byte aligned; read by the kernels at launch time, so a captured launch
+ * follows it from replay to replay */
+typedef struct drcvar_step_state {
+  uint64_t stream_offset;  /* the Philox stream words of this step's draw */
+  int64_t  step;           /* first path row of this step's window */
+} drcvar_step_state;
+
+/*
+ * The device-state form of drcvar_sampled_halfspaces_f64, for a receding-horizon loop replayed
+ * from one graph: the window's first path row and the stream offset are read from `state` when the
+ * kernel runs, not frozen at the call.
+ *
+ * nominal_path [n_obstacles, path_steps, 2] (strides nom_so, nom_st) and ego_path [path_steps, 2]
+ * (row stride ego_stride) are whole paths; the launch evaluates the window of n_steps = T rows that
+ * starts at s = state->step.  With c(i) = min(max(i, 0), path_steps - 1), window unit (o, t),
+ * u = o * T + t, uses nominal_path[o, c(s + t)] and ego_path[c(s + t)]: past either end of a path
+ * the obstacle and the ego hold the end row, and no value of `state` causes an out-of-range access.
+ * The Philox counter is u * ceil(N/2) + pair with the WINDOW-RELATIVE u, the stream words are
+ * state->stream_offset, the key is `seed`; zero_first_step applies to the window's t == 0 (the
+ * obstacle's current position is known, simulation/obstacles.py:63).
+ *
+ * The launch writes the same record bytes and status words as drcvar_sampled_halfspaces_f64 called
+ * on the gathered window nominal_path[:, c(s .. s+T-1)], ego_path[c(s .. s+T-1)] with
+ * stream_offset = state->stream_offset.  There is no samples_out.
+ *
+ * `state` is read with the kernel's first (scalar) load.  Whatever writes it — an earlier kernel or
+ * copy on the same stream, e.g. drcvar_mpc_step_advance_f64 (drcvar_mpc.h) — must precede this
+ * launch in stream order; nothing may write it while the launch runs.
+ *
+ * Host checks: those of drcvar_sampled_halfspaces_f64, and DRCVAR_ERR_INVALID_ARGUMENT for
+ * path_steps < 1, n_steps < 0, and (once there is something to launch) a `state` that is null or
+ * not 16-byte aligned.  unit_count == 0 or n_samples == 0: DRCVAR_OK, nothing launched.
+ */
+int drcvar_sampled_halfspaces_f64_dev(
+    const double* nominal_path, int64_t n_obstacles, int64_t path_steps, int64_t nom_so, int64_t nom_st,
+    int64_t n_steps,            /* window length T: units u = o * T + t, t = 0 .. T-1 */
+    int64_t unit_begin, int64_t unit_count, int64_t n_samples,
+    double l00, double l10, double l11, uint64_t seed,
+    const drcvar_step_state* state, int32_t zero_first_step,
+    const double* ego_path, int64_t ego_stride,   /* [path_steps, 2] */
+    double robot_radius, double obstacle_radius, double alpha, double delta, double epsilon,
+    double* out, int32_t* status, void* stream);
 
 /* host only: the plan a sample count runs on (threads per unit, Philox pairs per thread; a plan
  * holds 2 * threads * pairs samples); DRCVAR_ERR_UNSUPPORTED above DRCVAR_MAX_SAMPLES */
