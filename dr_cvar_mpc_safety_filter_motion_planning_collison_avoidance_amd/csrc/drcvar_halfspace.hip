@@ -27,8 +27,10 @@
 // Wave reductions use DPP row permutations + readlane (no LDS round trips).  Every reduction and
 // the candidate order are fixed, so results are bitwise reproducible run to run.
 // No MFMA: ~10 flops per 16-B sample — the kernel is bounded by HBM.
+#ifndef DRCVAR_HOST_PLANS_ONLY
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 
@@ -441,7 +443,13 @@ __device__ __forceinline__ void finish_offsets_peer(const PeerArgs& pa, unsigned
 //            instead of `out`
 //   FULL     small plans (P <= 8) only: the host saw N > BLOCK * (P - 1), so rows 0 .. P-2 hold a
 //            sample in every thread and carry no `i < n` selects; the last row keeps them
-template <int BLOCK, int P, int LOG_NB, int LOAD, bool GIVEN_H, bool PEER, bool FULL>
+//   LONE     small plans (P <= 8), not the peer or the nontemporal form: the host saw a grid of no
+//            more workgroups than the device has CUs, so this workgroup has its CU to itself and
+//            only its own chain counts — the candidate pass stores under a narrowed exec mask
+//            instead of behind a branch (append_candidate_masked).  On a full CU the branch is
+//            the cheaper form (1-3 % on C3 replicated to 2 GB), so larger grids keep it.
+template <int BLOCK, int P, int LOG_NB, int LOAD, bool GIVEN_H, bool PEER, bool FULL,
+          bool LONE = false>
 __global__ void __launch_bounds__(BLOCK)
 safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n,
                       int64_t s_obs, int64_t s_step, int64_t s_samp,
@@ -696,7 +704,8 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
     for (int j = 0; j < P; ++j) {
       const uint32_t cj = (code[j / 2] >> (16 * (j % 2))) & 0xFFFFu;
       sq += cj < ubin ? d[j] - mu_d : 0.0;
-      append_candidate(cregion, wbase, cj == ubin, d[j], lt_mask);
+      if constexpr (LONE) append_candidate_masked(cregion, wbase, cj == ubin, d[j], lt_mask);
+      else append_candidate(cregion, wbase, cj == ubin, d[j], lt_mask);
     }
     if constexpr (kPilot) {
       // small plans: this lane's tail partial goes to LDS unreduced; wave 0 reduces the four waves'
@@ -704,6 +713,7 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
       // reducing its own ahead of the barrier
       lane_tail[tid] = sq;
       if (lane == 0) wcount[wave] = wbase;
+      if constexpr (LONE) lds_masked_wait();  // the masked candidate stores, ahead of barrier 3
     } else {
       sq = wave_reduce<OpAdd>(sq);
       if (lane == 0) {
@@ -897,6 +907,11 @@ safe_halfspace_stream_kernel(const double* __restrict__ samples, int64_t n_steps
 // ---------------------------------------------------------------------------------------------
 // launch plans
 // ---------------------------------------------------------------------------------------------
+#endif  // !DRCVAR_HOST_PLANS_ONLY
+// The host's choice of launch plan and kernel form: plain C++, no HIP, nothing but <cstdint> and
+// drcvar_halfspace.h before it.  With -DDRCVAR_HOST_PLANS_ONLY this section is all of the file that
+// is compiled: tests/test_halfspace_form_host.py includes the file that way into a stand-alone
+// program of the host compiler and checks the rule without a GPU.
 struct Plan {
   int block, per, log_nb;
   bool automatic;  // part of the default chain (smallest automatic plan with block*per >= N)
@@ -920,7 +935,7 @@ constexpr Plan kPlans[] = {
 };
 constexpr int kNumPlans = sizeof(kPlans) / sizeof(kPlans[0]);
 
-int pick_plan(int64_t n, int threads, int per) {
+inline int pick_plan(int64_t n, int threads, int per) {
   for (int p = 0; p < kNumPlans; ++p) {
     const Plan& pl = kPlans[p];
     if (n > static_cast<int64_t>(pl.block) * pl.per) continue;
@@ -933,6 +948,34 @@ int pick_plan(int64_t n, int threads, int per) {
   return -1;
 }
 
+// The two forms of the kernel.  LONE: the candidate pass stores under a narrowed exec mask
+// instead of behind a branch — faster for a workgroup that has its CU to itself, slower where the
+// CUs are full (docs/lab_notebook.md section 4).  The whole rule is here: the plans that have the
+// form (those holding at most kLoneMaxPer samples per thread, not the peer form), and the launches
+// that take it (no more units than the device has CUs, so no CU gets a second workgroup).
+constexpr int kFormShared = 0, kFormLone = 1;
+constexpr int kLoneMaxPer = 8;
+constexpr bool lone_capable(int per, bool peer) { return per <= kLoneMaxPer && !peer; }
+constexpr bool lone_form(int per, bool peer, int64_t units, int cu_count) {
+  return lone_capable(per, peer) && units >= 1 && units <= cu_count;
+}
+
+// The form an automatic, non-peer launch of n_units units of n_samples samples takes on a device
+// with cu_count CUs (what dispatch computes, with the argument checks of drcvar_launch_plan).
+inline int halfspace_form(int64_t n_samples, int64_t n_units, int32_t cu_count, int32_t* form) {
+  if (n_samples < 1 || n_units < 0 || cu_count < 1 || !form) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (n_samples > DRCVAR_MAX_SAMPLES) {  // the streaming kernel has one form
+    if (n_samples > DRCVAR_MAX_SAMPLES_STREAM) return DRCVAR_ERR_UNSUPPORTED;
+    *form = kFormShared;
+    return DRCVAR_OK;
+  }
+  const int p = pick_plan(n_samples, 0, 0);
+  if (p < 0) return DRCVAR_ERR_UNSUPPORTED;
+  *form = lone_form(kPlans[p].per, false, n_units, cu_count) ? kFormLone : kFormShared;
+  return DRCVAR_OK;
+}
+#ifndef DRCVAR_HOST_PLANS_ONLY
+
 struct Launch {
   const double* samples;
   int64_t units, n_steps, n, s_obs, s_step, s_samp;
@@ -943,13 +986,37 @@ struct Launch {
   int32_t* status;  // [units] or null
   hipStream_t stream;
   PeerArgs peer;    // the peer form only
+  bool lone;        // no more units than the device has CUs (dispatch)
 };
+
+// CUs of the calling thread's current device, asked once per device and cached: two attribute
+// queries, no allocation, no synchronisation, nothing a stream capture forbids — a process whose
+// first launch is captured into a graph gets its answer the same way.  The launch is assumed to
+// run on the current device (bench.py, the tests and the drop-in layer all make the device of
+// their tensors current); a stream of another device would only have its form chosen by this
+// device's CU count, never get other results.  0 (never the LONE
+// form) if the runtime does not answer.
+constexpr int kMaxDevices = 64;
+std::atomic<int> g_cu_count[kMaxDevices];
+int device_cu_count() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 0;
+  int cus = g_cu_count[dev].load(std::memory_order_relaxed);
+  if (cus == 0) {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus < 0)
+      cus = 0;
+    g_cu_count[dev].store(cus, std::memory_order_relaxed);
+  }
+  return cus;
+}
 
 // grid (n_steps, obstacles), at most kMaxGridY obstacles per launch (the y-dimension limit):
 // larger batches are split into obstacle chunks on the host
 constexpr int64_t kMaxGridY = 65535;
 
-template <int BLOCK, int P, int LOG_NB, int LOAD, bool GIVEN_H, bool PEER, bool FULL>
+template <int BLOCK, int P, int LOG_NB, int LOAD, bool GIVEN_H, bool PEER, bool FULL,
+          bool LONE = false>
 int launch_form(const Launch& L) {
   const int64_t n_obs = L.units / L.n_steps;
   const size_t dyn = 0;
@@ -957,7 +1024,7 @@ int launch_form(const Launch& L) {
     const int64_t chunk = n_obs - o0 < kMaxGridY ? n_obs - o0 : kMaxGridY;
     PeerArgs pa = L.peer;
     pa.row_base += o0 * L.n_steps;
-    hipLaunchKernelGGL((safe_halfspace_kernel<BLOCK, P, LOG_NB, LOAD, GIVEN_H, PEER, FULL>),
+    hipLaunchKernelGGL((safe_halfspace_kernel<BLOCK, P, LOG_NB, LOAD, GIVEN_H, PEER, FULL, LONE>),
                        dim3(static_cast<unsigned>(L.n_steps), static_cast<unsigned>(chunk)),
                        dim3(BLOCK), dyn, L.stream, L.samples + o0 * L.s_obs, L.n_steps,
                        static_cast<int>(L.n), L.s_obs, L.s_step, L.s_samp,
@@ -970,11 +1037,19 @@ int launch_form(const Launch& L) {
 
 // Small plans whose N fills every row but the last run the form without those rows' `i < n`
 // selects; any other N (an explicit geometry far larger than N included) the predicated form.
+// Either in the LONE form when dispatch found the launch to meet lone_form
+// (above); a launch of that size is far below the nontemporal form's 256 MB.
 template <int BLOCK, int P, int LOG_NB, int LOAD, bool GIVEN_H, bool PEER>
 int launch_rows(const Launch& L) {
   if constexpr (P <= 8) {
-    if (L.n > static_cast<int64_t>(BLOCK) * (P - 1))
-      return launch_form<BLOCK, P, LOG_NB, LOAD, GIVEN_H, PEER, true>(L);
+    const bool full = L.n > static_cast<int64_t>(BLOCK) * (P - 1);
+    if constexpr (lone_capable(P, PEER) && LOAD != kLoadNt) {
+      if (L.lone) {
+        return full ? launch_form<BLOCK, P, LOG_NB, LOAD, GIVEN_H, PEER, true, true>(L)
+                    : launch_form<BLOCK, P, LOG_NB, LOAD, GIVEN_H, PEER, false, true>(L);
+      }
+    }
+    if (full) return launch_form<BLOCK, P, LOG_NB, LOAD, GIVEN_H, PEER, true>(L);
   }
   return launch_form<BLOCK, P, LOG_NB, LOAD, GIVEN_H, PEER, false>(L);
 }
@@ -1008,7 +1083,7 @@ void launch_stream(const Launch& L, bool vec) {
 }
 
 template <bool GIVEN_H, bool PEER = false>
-int dispatch(const Launch& L, int threads, int per) {
+int dispatch(Launch L, int threads, int per) {
   if (L.units == 0) return DRCVAR_OK;
   const bool vec = (reinterpret_cast<uintptr_t>(L.samples) % 16 == 0) && (L.s_obs % 2 == 0) &&
                    (L.s_step % 2 == 0) && (L.s_samp % 2 == 0);
@@ -1022,6 +1097,7 @@ int dispatch(const Launch& L, int threads, int per) {
   const int p = pick_plan(L.n, threads, per);
   if (p < 0) return DRCVAR_ERR_UNSUPPORTED;
   (void)hipGetLastError();  // clear stale errors from unrelated work
+  L.lone = lone_form(kPlans[p].per, PEER, L.units, device_cu_count());
   int rc = DRCVAR_OK;
   switch (p) {
     case 0: rc = launch_plan<64, 2, 7, GIVEN_H, PEER>(L, vec); break;
@@ -1209,3 +1285,4 @@ int drcvar_offsets_given_h_f64(const double* samples, int64_t n_units, int64_t n
 }
 
 }  // extern "C"
+#endif  // !DRCVAR_HOST_PLANS_ONLY

@@ -356,6 +356,44 @@ __device__ __forceinline__ void append_candidate(double* region, uint32_t& wbase
   wbase += static_cast<uint32_t>(__popcll(ballot));
 }
 
+// The LDS byte address of a pointer into a __shared__ array (what a DS instruction takes).
+__device__ __forceinline__ uint32_t lds_address(const void* p) {
+  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>(
+      (const __attribute__((address_space(3))) void*)p));
+}
+
+// append_candidate without its branch, for a workgroup that has its CU to itself (the kernel's
+// LONE form): every lane computes its slot, and the one ds_write_b64 is issued under an exec mask
+// narrowed to the ballot for that single instruction (saved, narrowed, restored inside one asm
+// block), so the pass is straight-line code — the compiler keeps an s_cbranch_execz around any
+// conditional block that holds a DS instruction.  On a full CU that skip is the cheaper form (a
+// wave without a candidate issues nothing for the row); alone on a CU only the wave's own chain
+// counts, and the branch is what costs.  Preconditions: all 64 lanes active on entry (BLOCK a
+// multiple of 64, the call under uniform branches only); `region` points into LDS.  A zero ballot
+// is legal: the store issues with an empty mask and writes nothing.  A lane outside the ballot
+// never stores, so its slot (below wbase + 64) need not lie inside the region.
+// The compiler does not count this store in lgkmcnt: a caller waits with lds_masked_wait() ahead
+// of the barrier that publishes the region.
+__device__ __forceinline__ void append_candidate_masked(double* region, uint32_t& wbase,
+                                                        bool is_cand, double v,
+                                                        unsigned long long lt_mask) {
+  const unsigned long long ballot = __ballot(is_cand);
+  const uint32_t addr = lds_address(region + wbase + __popcll(ballot & lt_mask));
+  unsigned long long saved;
+  asm volatile(
+      "s_and_saveexec_b64 %0, %1\n\t"
+      "ds_write_b64 %2, %3\n\t"
+      "s_mov_b64 exec, %0"
+      : "=&s"(saved)
+      : "s"(ballot), "v"(addr), "v"(v)
+      : "memory", "scc");
+  wbase += static_cast<uint32_t>(__popcll(ballot));
+}
+
+// Every LDS operation of this wave has completed, the masked stores (which the compiler does not
+// see) included: ahead of the barrier that publishes what they wrote.
+__device__ __forceinline__ void lds_masked_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
 // Wave 0 (all lanes active), a target bucket of c <= 64 / NW candidates: no wave holds more than
 // E = 64 / NW of them, so wave w appends its candidates to the segment cand[w * E + k] and all of
 // the unit's candidates lie in cand[0 .. 64), in rank_candidates' order (wave, then position)
