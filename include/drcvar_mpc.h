@@ -216,6 +216,11 @@ int drcvar_mpc_filter_f64_ex(const drcvar_mpc_model* model, const double* blob, 
  *                     without: u_fallback[k] = u_ref_path[c(s' + k)]
  *   7. state          state->step = s', state->stream_offset += 1 (wrapping at 2^64)
  * No value of `state` causes an out-of-range access (s' past the paths' end holds their last row).
+ * Exactly, for any s: the stored step wraps at 2^63 as the offset wraps at 2^64 (s = 2^63 - 1 is
+ * followed by -2^63); i is the wrapped difference (s - step_begin) mod 2^64, and "0 <= i < log_rows"
+ * means that this number is below log_rows (step_begin = 2^63 - 1, s = -2^63: i = 1); the windows of
+ * steps 5 and 6 are taken from the unwrapped s + 1 + k, so at s = 2^63 - 1 every row is the paths'
+ * last one.  A step that is not logged is otherwise a full step: steps 3 to 7 run all the same.
  *
  *   x_out [H+1, nx], u_out [H, nu], info [DRCVAR_MPC_INFO_WIDTH]   the solver's outputs (dense)
  *   x_ref_path [path_steps, nx], u_ref_path [path_steps, nu]       read-only paths (dense)
