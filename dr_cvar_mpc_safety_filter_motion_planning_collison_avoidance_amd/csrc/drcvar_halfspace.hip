@@ -39,7 +39,6 @@
 
 namespace {
 
-constexpr double kSentinel = 100.0;
 // sample load forms (kernel template)
 constexpr int kLoadPair = 0, kLoadVec = 1, kLoadNt = 2;
 constexpr int64_t kNtBytes = 256ll << 20;  // launches reading more than the MALL use kLoadNt
@@ -83,31 +82,14 @@ __device__ unsigned long long g_stamps[kStampUnits * kStamps];
   } while (0)
 #endif
 
-// the selection toolkit shared with drcvar_sampled.hip: Params, reductions, histogram scan, ranking
+// the selection toolkit shared with drcvar_sampled.hip: Params, reductions, histogram scan, ranking,
+// the exact fallback, the offsets
 #include "drcvar_selection.inc"
 
-// fp32 sum over the wave, same tree (the DPP moves fold into v_add_f32_dpp): ~60 cycles per value.
-__device__ __forceinline__ float wave_sum_f32(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), kDppQuadXor1, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), kDppQuadXor2, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), kDppHalfMirror, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), kDppMirror, 0xF, 0xF, false));
-  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_int(v), __float_as_int(v), false, false);
-  v = __int_as_float(a[0]) + __int_as_float(a[1]);
-  const auto b = __builtin_amdgcn_permlane32_swap(__float_as_int(v), __float_as_int(v), false, false);
-  return uniform_f32(__int_as_float(b[0]) + __int_as_float(b[1]));
-}
-
-// KD fp64 and KF fp32 wave sums at once: the same trees as wave_reduce / wave_sum_f32 (so the
+// KD fp64 and KF fp32 wave sums at once: the same trees as wave_reduce and its fp32 twin (so the
 // results are bitwise those of the one-value forms), written stage by stage across the values so
 // that the independent chains fill each other's DPP hazard slots (one value at a time, the
 // compiler emitted the seven chains back to back: ~750 cycles on the critical path of barrier 1).
-template <int CTRL>
-__device__ __forceinline__ double mov_dpp_f64(double v) {
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
 template <int CTRL>
 __device__ __forceinline__ float mov_dpp_f32(float v) {
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, false));
@@ -117,7 +99,7 @@ __device__ __forceinline__ void sum_stage(double* v, float* f) {
   double td[KD > 0 ? KD : 1];
   float tf[KF > 0 ? KF : 1];
 #pragma unroll
-  for (int q = 0; q < KD; ++q) td[q] = mov_dpp_f64<CTRL>(v[q]);
+  for (int q = 0; q < KD; ++q) td[q] = dpp_f64<CTRL>(v[q]);
 #pragma unroll
   for (int q = 0; q < KF; ++q) tf[q] = mov_dpp_f32<CTRL>(f[q]);
 #pragma unroll
@@ -205,12 +187,11 @@ __device__ __forceinline__ void write_mean_halfspace(double* rec, double mux, do
 }
 
 __device__ __forceinline__ void store_record(double* rec, double m0, double m1, double gm,
-                                             double h0, double h1, double gc, double gs,
-                                             double gt) {
+                                             double h0, double h1, const Offsets& g) {
   reinterpret_cast<double2*>(rec)[0] = make_double2(m0, m1);
   reinterpret_cast<double2*>(rec)[1] = make_double2(gm, h0);
-  reinterpret_cast<double2*>(rec)[2] = make_double2(h1, gc);
-  reinterpret_cast<double2*>(rec)[3] = make_double2(gs, gt);
+  reinterpret_cast<double2*>(rec)[2] = make_double2(h1, g.g_cvar);
+  reinterpret_cast<double2*>(rec)[3] = make_double2(g.g_star, g.g_tilde);
 }
 
 // The peer-push exchange (drcvar_safe_halfspaces_f64_peer, include/drcvar_exchange.h): every
@@ -235,8 +216,8 @@ __device__ __forceinline__ void store_sys(double* p, double v) {
 // the wave).  Parity = (completed steps + 1) & 1: the buffer this step fills.
 __device__ __forceinline__ void peer_store_record(const PeerArgs& pa, unsigned long long gen,
                                                   int64_t u, int lane, double m0, double m1,
-                                                  double gm, double h0, double h1, double gc,
-                                                  double gs, double gt) {
+                                                  double gm, double h0, double h1,
+                                                  const Offsets& g) {
   if (lane < pa.n_ranks) {
     const int64_t parity = static_cast<int64_t>((gen + 1ull) & 1ull);
     double* r = pa.region[lane] + (parity * pa.rows + pa.row_base + u) * DRCVAR_OUT_WIDTH;
@@ -245,9 +226,9 @@ __device__ __forceinline__ void peer_store_record(const PeerArgs& pa, unsigned l
     store_sys(r + 2, gm);
     store_sys(r + 3, h0);
     store_sys(r + 4, h1);
-    store_sys(r + 5, gc);
-    store_sys(r + 6, gs);
-    store_sys(r + 7, gt);
+    store_sys(r + 5, g.g_cvar);
+    store_sys(r + 6, g.g_star);
+    store_sys(r + 7, g.g_tilde);
   }
   // every record store acknowledged (system scope: performed in the destination's memory) before
   // the wave ends, so the publish launch behind this one finds them all in place
@@ -266,121 +247,10 @@ __device__ __forceinline__ double project_at(const double* base, int i, int64_t 
   }
 }
 
-// LDS accesses of one wave complete in order; this keeps the compiler from moving them across a
-// wave-local hand-off (no barrier needed within a wave)
-__device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
-
-// Lane w < NW: the candidate count of wave w (0 elsewhere) — the ranking's input, read by the
-// caller so that it can be issued together with other LDS reads.
-template <int NW>
-__device__ __forceinline__ uint32_t wave_counts(const uint32_t* wcount, int lane) {
-  return lane < NW ? wcount[lane] : 0u;
-}
 // Makes a loaded value available at this point (an empty asm that consumes it): keeps the compiler
 // from sinking independent LDS loads past a branch or a wait, so they share one round trip.
 __device__ __forceinline__ void lds_values_ready(uint32_t v) { asm volatile("" ::"v"(v)); }
 __device__ __forceinline__ void lds_values_ready(double v) { asm volatile("" ::"v"(v)); }
-
-// Exact selection for the units the register fast path does not finish (degenerate moments, or a
-// first-pass bucket with more than kCap samples).  It re-reads the unit's samples (L2/MALL-hot)
-// instead of keeping register state live: exact min/max, then histogram refinement (value-linear,
-// then order-preserving integer keys) until <= kCap candidates remain or the run collapses to one
-// value.  Result (valid in wave 0): tau and dsum = sum_{d<tau} (d - tau).
-// proj(i): the projection h . xi_i of sample i (re-read from memory).
-template <int BLOCK, int LOG_NB, class Proj>
-__device__ __forceinline__ void select_from_memory(const Proj& proj, int n, double mu_d,
-                                                uint32_t rank, uint32_t* hist, double* cand,
-                                                uint32_t* wcount, double* red_rng,
-                                                double* red_tail, double* tau_out,
-                                                double* dsum_out) {
-  constexpr int NW = BLOCK / kWave;
-  constexpr int NB = 1 << LOG_NB;
-  const int tid = threadIdx.x;
-  const int lane = tid & (kWave - 1);
-  const int wave = tid / kWave;
-  __syncthreads();  // the fast path's readers of hist / red_* are done
-
-  double vmin[1] = {INFINITY}, vmax[1] = {-INFINITY};
-  for (int i = tid; i < n; i += BLOCK) {
-    const double v = proj(i);
-    vmin[0] = fmin(vmin[0], v);
-    vmax[0] = fmax(vmax[0], v);
-  }
-  block_reduce<OpMin, NW, 1>(vmin, red_rng);
-  block_reduce<OpMax, NW, 1>(vmax, red_rng + NW);
-  double lo = vmin[0], hi = vmax[0];
-  if (lo == hi) {  // every sample projects to one value (the noise-free step 0): no tail below it
-    *tau_out = lo;
-    *dsum_out = 0.0;
-    return;        // uniform; no second pass over the samples
-  }
-  uint32_t rr = rank, c = static_cast<uint32_t>(n);
-  bool have_bin = false, tau_known = false;
-  double tau = lo;
-  int bin = 0;
-  BucketMap<LOG_NB> map;
-  for (int iter = 0; !tau_known; ++iter) {
-    map.init_range(lo, hi, iter);
-    for (int b = tid; b < hist_words<NB>(); b += BLOCK) hist[b] = 0u;
-    __syncthreads();
-    for (int i = tid; i < n; i += BLOCK) {
-      const double v = proj(i);
-      if (in_range(v, lo, hi)) atomicAdd(&hist[hist_slot<NB>(map(v))], 1u);
-    }
-    __syncthreads();
-    const ScanResult sr = scan_bins<NB>(hist, rr, lane);
-    bin = sr.bin;
-    rr -= sr.below;
-    c = sr.cnt;
-    have_bin = true;
-    if (c <= kCap) break;
-    double rmin[1] = {INFINITY}, rmax[1] = {-INFINITY};
-    for (int i = tid; i < n; i += BLOCK) {
-      const double v = proj(i);
-      if (in_range(v, lo, hi) && map(v) == bin) {
-        rmin[0] = fmin(rmin[0], v);
-        rmax[0] = fmax(rmax[0], v);
-      }
-    }
-    __syncthreads();  // all waves have scanned hist before it is cleared again
-    block_reduce<OpMin, NW, 1>(rmin, red_rng);
-    block_reduce<OpMax, NW, 1>(rmax, red_rng + NW);
-    lo = rmin[0];
-    hi = rmax[0];
-    have_bin = false;
-    if (lo == hi) {
-      tau_known = true;
-      tau = lo;
-    }
-  }
-
-  double sq = 0.0;
-  uint32_t wbase = 0;
-  const unsigned long long lt_mask = (1ull << lane) - 1ull;
-  for (int i0 = 0; i0 < n; i0 += BLOCK) {  // uniform trip count: ballots see whole waves
-    const int i = i0 + tid;
-    const double v = i < n ? proj(i) : NAN;
-    const bool inr = in_range(v, lo, hi);
-    const int bj = (have_bin && inr) ? map(v) : 0;
-    const bool below = v < lo || (have_bin && inr && bj < bin);
-    if (below) sq += v - mu_d;
-    append_candidate(cand + wave * kCap, wbase, !tau_known && inr && (!have_bin || bj == bin), v,
-                     lt_mask);
-  }
-  sq = wave_reduce<OpAdd>(sq);
-  if (lane == 0) {
-    red_tail[wave] = sq;
-    wcount[wave] = wbase;
-  }
-  __syncthreads();
-  if (wave != 0) return;
-  const double s_below = sum_partials<NW>(red_tail);
-  double s_cand = 0.0;
-  if (!tau_known) tau = rank_candidates<NW>(cand, wave_counts<NW>(wcount, lane), c, rr, lane, &s_cand);
-  const double n_below = static_cast<double>(rank - rr);
-  *tau_out = tau;
-  *dsum_out = (s_below - n_below * (tau - mu_d)) + s_cand;
-}
 
 // Offsets from the lower-tail statistics (wave 0, lane 0 writes).  L = tau + dsum / k.
 // (The peer form below computes the same values in every lane of wave 0, from lane 0's tau and
@@ -391,21 +261,15 @@ __device__ __forceinline__ void finish_offsets(double* rec, const Params& prm, d
                                                double h1, double tau, double dsum, double mux,
                                                double muy, int lane) {
   if (lane == 0) {
-    const double L = tau + dsum * prm.inv_k;  // lower-tail mean
-    const double g_cvar = r - prm.delta - L;
-    double g_star = kSentinel, g_tilde = kSentinel - r;
-    if (prm.epsilon >= 0.0) {  // else: DR LP unbounded (lambda -> inf), solver-failure sentinel
-      g_star = r - prm.delta + prm.eps_over_alpha - L;
-      g_tilde = g_star - r;
-    }
+    const Offsets g = offsets_from_tail(prm, r, tau, dsum);
     if constexpr (NW == 1) {
       double m0, m1, g_mean;
       mean_halfspace(mux, muy, prm.rc, &m0, &m1, &g_mean);
-      store_record(rec, m0, m1, g_mean, h0, h1, g_cvar, g_star, g_tilde);
+      store_record(rec, m0, m1, g_mean, h0, h1, g);
     } else {  // columns 0..2 are written by wave 1
       reinterpret_cast<double*>(rec)[DRCVAR_COL_H0] = h0;
-      reinterpret_cast<double2*>(rec)[2] = make_double2(h1, g_cvar);
-      reinterpret_cast<double2*>(rec)[3] = make_double2(g_star, g_tilde);
+      reinterpret_cast<double2*>(rec)[2] = make_double2(h1, g.g_cvar);
+      reinterpret_cast<double2*>(rec)[3] = make_double2(g.g_star, g.g_tilde);
     }
   }
 }
@@ -416,16 +280,10 @@ __device__ __forceinline__ void finish_offsets_peer(const PeerArgs& pa, unsigned
                                                     double mux, double muy, int lane) {
   tau = readlane_f64(tau, 0);
   dsum = readlane_f64(dsum, 0);
-  const double L = tau + dsum * prm.inv_k;
-  const double g_cvar = r - prm.delta - L;
-  double g_star = kSentinel, g_tilde = kSentinel - r;
-  if (prm.epsilon >= 0.0) {
-    g_star = r - prm.delta + prm.eps_over_alpha - L;
-    g_tilde = g_star - r;
-  }
+  const Offsets g = offsets_from_tail(prm, r, tau, dsum);
   double m0, m1, g_mean;
   mean_halfspace(mux, muy, prm.rc, &m0, &m1, &g_mean);
-  peer_store_record(pa, gen, u, lane, m0, m1, g_mean, h0, h1, g_cvar, g_star, g_tilde);
+  peer_store_record(pa, gen, u, lane, m0, m1, g_mean, h0, h1, g);
 }
 
 
@@ -590,8 +448,7 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
         const double r = prm.rc * norm_h(h0, h1);  // R_c |h|
         double m0, m1, g_mean;
         mean_halfspace(mux, muy, prm.rc, &m0, &m1, &g_mean);
-        peer_store_record(peer, gen, u, lane, m0, m1, g_mean, h0, h1, kSentinel, kSentinel,
-                          kSentinel - r);
+        peer_store_record(peer, gen, u, lane, m0, m1, g_mean, h0, h1, failure_offsets(r));
         if (status && lane == 0) status[u] = failure_status(bad, prm);
       }
       return;
@@ -600,7 +457,7 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
       const double r = prm.rc * norm_h(h0, h1);  // R_c |h|
       double m0, m1, g_mean;
       mean_halfspace(mux, muy, prm.rc, &m0, &m1, &g_mean);
-      store_record(rec, m0, m1, g_mean, h0, h1, kSentinel, kSentinel, kSentinel - r);
+      store_record(rec, m0, m1, g_mean, h0, h1, failure_offsets(r));
       if (status) status[u] = failure_status(bad, prm);
     }
     return;  // uniform across the workgroup
@@ -802,8 +659,8 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
     }
     if (!settled) {
       const auto proj = [&](int i) { return project_at<LOAD != kLoadPair>(base, i, s_samp, h0, h1); };
-      select_from_memory<BLOCK, LOG_NB>(proj, n, mu_d, rank, hist, cand, wcount, red_rng, red_tail,
-                                        &tau, &dsum);
+      select_exact<BLOCK, LOG_NB>(memory_source<BLOCK>(proj, n), mu_d, rank, hist, cand, wcount,
+                                  red_rng, red_tail, &tau, &dsum);
     }
     if (wave != 0) {
       if (!PEER && wave == 1) write_mean_halfspace(rec, mux, muy, prm.rc, lane);
@@ -826,8 +683,8 @@ safe_halfspace_kernel(const double* __restrict__ samples, int64_t n_steps, int n
 
 // ---------------------------------------------------------------------------------------------
 // streaming variant for N > DRCVAR_MAX_SAMPLES: nothing is held in registers — the mean is a
-// strided pass over the unit's samples and the order statistic comes from select_from_memory's
-// exact histogram refinement over re-reads (min/max pass, ~1 histogram pass per factor 10^3 of
+// strided pass over the unit's samples and the order statistic comes from select_exact's
+// histogram refinement over re-reads (min/max pass, ~1 histogram pass per factor 10^3 of
 // N, a candidate pass).  Any N up to 2^31 - 1; ~4 reads of the unit instead of 1.
 // ---------------------------------------------------------------------------------------------
 constexpr int kStreamBlock = 1024;
@@ -883,10 +740,9 @@ safe_halfspace_stream_kernel(const double* __restrict__ samples, int64_t n_steps
   const double rch = prm.rc * norm_h(h0, h1);  // R_c |h|
   if (bad || prm.unbounded) {
     if (tid == 0) {
-      const double r = rch;
       double m0, m1, g_mean;
       mean_halfspace(mux, muy, prm.rc, &m0, &m1, &g_mean);
-      store_record(rec, m0, m1, g_mean, h0, h1, kSentinel, kSentinel, kSentinel - r);
+      store_record(rec, m0, m1, g_mean, h0, h1, failure_offsets(rch));
       if (status) status[u] = failure_status(bad, prm);
     }
     return;
@@ -894,8 +750,8 @@ safe_halfspace_stream_kernel(const double* __restrict__ samples, int64_t n_steps
   const double mu_d = h0 * mux + h1 * muy;
   double tau, dsum;
   const auto proj = [&](int i) { return project_at<VEC>(base, i, s_samp, h0, h1); };
-  select_from_memory<BLOCK, kStreamLogNB>(proj, n, mu_d, prm.rank, hist,
-                                               cand, wcount, red_rng, red_tail, &tau, &dsum);
+  select_exact<BLOCK, kStreamLogNB>(memory_source<BLOCK>(proj, n), mu_d, prm.rank, hist, cand,
+                                    wcount, red_rng, red_tail, &tau, &dsum);
   if (wave != 0) {
     if (wave == 1) write_mean_halfspace(rec, mux, muy, prm.rc, lane);
     return;

@@ -45,8 +45,6 @@
 
 namespace {
 
-constexpr double kSentinel = 100.0;
-
 #include "drcvar_generator.inc"  // the draw: Philox, Box-Muller, the LDS tables, draw_pair
 #include "drcvar_selection.inc"  // Params and the selection toolkit of the stored form
 
@@ -62,8 +60,7 @@ struct DrawArgs {
 
 // The whole record by one lane, plain stores.
 __device__ __forceinline__ void store_record(double* rec, double mux, double muy, double rc,
-                                             double h0, double h1, double gc, double gs,
-                                             double gt) {
+                                             double h0, double h1, const Offsets& g) {
   double m0, m1, gm;
   mean_halfspace(mux, muy, rc, &m0, &m1, &gm);
   rec[DRCVAR_COL_MEAN_H0] = m0;
@@ -71,114 +68,9 @@ __device__ __forceinline__ void store_record(double* rec, double mux, double muy
   rec[DRCVAR_COL_G_MEAN] = gm;
   rec[DRCVAR_COL_H0] = h0;
   rec[DRCVAR_COL_H1] = h1;
-  rec[DRCVAR_COL_G_CVAR] = gc;
-  rec[DRCVAR_COL_G_DR_STAR] = gs;
-  rec[DRCVAR_COL_G_DR_TILDE] = gt;
-}
-
-// Exact selection over the register-held projections d[0..Q) (bit q of vmask: slot q holds a
-// sample), for the units the window does not finish.  The structure of the stored form's
-// select_from_memory with its re-reads replaced by the registers: exact min/max, then histogram
-// refinement (value-linear, then order-preserving integer keys) until <= kCap candidates remain or
-// the run collapses to one value.  Result (valid in wave 0): tau and dsum = sum_{d<tau} (d - tau).
-template <int BLOCK, int LOG_NB, int Q>
-__device__ __forceinline__ void select_from_registers(const double (&d)[Q], uint32_t vmask,
-                                                      double mu_d, uint32_t rank, uint32_t* hist,
-                                                      double* cand, uint32_t* wcount,
-                                                      double* red_rng, double* red_tail,
-                                                      double* tau_out, double* dsum_out) {
-  constexpr int NW = BLOCK / kWave;
-  constexpr int NB = 1 << LOG_NB;
-  const int tid = threadIdx.x;
-  const int lane = tid & (kWave - 1);
-  const int wave = tid / kWave;
-  __syncthreads();  // the window path's readers of hist are done
-
-  double vmin[1] = {INFINITY}, vmax[1] = {-INFINITY};
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    if ((vmask >> q) & 1u) {
-      vmin[0] = fmin(vmin[0], d[q]);
-      vmax[0] = fmax(vmax[0], d[q]);
-    }
-  }
-  block_reduce<OpMin, NW, 1>(vmin, red_rng);
-  block_reduce<OpMax, NW, 1>(vmax, red_rng + NW);
-  double lo = vmin[0], hi = vmax[0];
-  if (lo == hi) {  // every sample projects to one value: no tail below it
-    *tau_out = lo;
-    *dsum_out = 0.0;
-    return;  // uniform
-  }
-  uint32_t rr = rank, c = 0;
-  bool have_bin = false, tau_known = false;
-  double tau = lo;
-  int bin = 0;
-  BucketMap<LOG_NB> map;
-  for (int iter = 0; !tau_known; ++iter) {
-    map.init_range(lo, hi, iter);
-    for (int b = tid; b < hist_words<NB>(); b += BLOCK) hist[b] = 0u;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      const double v = ((vmask >> q) & 1u) ? d[q] : NAN;
-      if (in_range(v, lo, hi)) atomicAdd(&hist[hist_slot<NB>(map(v))], 1u);
-    }
-    __syncthreads();
-    const ScanResult sr = scan_bins<NB>(hist, rr, lane);
-    bin = sr.bin;
-    rr -= sr.below;
-    c = sr.cnt;
-    have_bin = true;
-    if (c <= kCap) break;
-    double rmin[1] = {INFINITY}, rmax[1] = {-INFINITY};
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      const double v = ((vmask >> q) & 1u) ? d[q] : NAN;
-      if (in_range(v, lo, hi) && map(v) == bin) {
-        rmin[0] = fmin(rmin[0], v);
-        rmax[0] = fmax(rmax[0], v);
-      }
-    }
-    __syncthreads();  // all waves have scanned hist before it is cleared again
-    block_reduce<OpMin, NW, 1>(rmin, red_rng);
-    block_reduce<OpMax, NW, 1>(rmax, red_rng + NW);
-    lo = rmin[0];
-    hi = rmax[0];
-    have_bin = false;
-    if (lo == hi) {
-      tau_known = true;
-      tau = lo;
-    }
-  }
-
-  double sq = 0.0;
-  uint32_t wbase = 0;
-  const unsigned long long lt_mask = (1ull << lane) - 1ull;
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {  // uniform trip count: ballots see whole waves
-    const double v = ((vmask >> q) & 1u) ? d[q] : NAN;
-    const bool inr = in_range(v, lo, hi);
-    const int bj = (have_bin && inr) ? map(v) : 0;
-    const bool below = v < lo || (have_bin && inr && bj < bin);
-    if (below) sq += v - mu_d;
-    append_candidate(cand + wave * kCap, wbase, !tau_known && inr && (!have_bin || bj == bin), v,
-                     lt_mask);
-  }
-  sq = wave_reduce<OpAdd>(sq);
-  if (lane == 0) {
-    red_tail[wave] = sq;
-    wcount[wave] = wbase;
-  }
-  __syncthreads();
-  if (wave != 0) return;
-  const double s_below = sum_partials<NW>(red_tail);
-  double s_cand = 0.0;
-  if (!tau_known)
-    tau = rank_candidates<NW>(cand, lane < NW ? wcount[lane] : 0u, c, rr, lane, &s_cand);
-  const double n_below = static_cast<double>(rank - rr);
-  *tau_out = tau;
-  *dsum_out = (s_below - n_below * (tau - mu_d)) + s_cand;
+  rec[DRCVAR_COL_G_CVAR] = g.g_cvar;
+  rec[DRCVAR_COL_G_DR_STAR] = g.g_star;
+  rec[DRCVAR_COL_G_DR_TILDE] = g.g_tilde;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -327,7 +219,7 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
   if (bad || prm.unbounded) {  // risk_metrics.py:298-303,334-338
     if (tid == 0) {
       const double r = prm.rc * norm_h(h0, h1);
-      store_record(rec, mux, muy, prm.rc, h0, h1, kSentinel, kSentinel, kSentinel - r);
+      store_record(rec, mux, muy, prm.rc, h0, h1, failure_offsets(r));
       if (status) status[row] = failure_status(bad, prm);
     }
     return;  // uniform across the workgroup
@@ -410,8 +302,8 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
     dsum = (s_below - static_cast<double>(rank - rr) * (tau - mu_d)) + s_cand;
   } else {
     if (noisy) {
-      select_from_registers<BLOCK, LOG_NB, Q>(d, vmask, mu_d, rank, hist, cand, wcount, red_rng,
-                                              red_tail, &tau, &dsum);
+      select_exact<BLOCK, LOG_NB>(RegisterSource<Q>{d, vmask}, mu_d, rank, hist, cand, wcount,
+                                  red_rng, red_tail, &tau, &dsum);
     } else {  // every sample is the nominal point: tau = its projection, no tail below it
       tau = project(h0, h1, nx, ny);
       dsum = 0.0;
@@ -422,14 +314,7 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
   // ---- 5. offsets (wave 0, lane 0) -------------------------------------------------------------
   if (lane == 0) {
     const double r = prm.rc * norm_h(h0, h1);  // R_c |h| (risk_metrics.py:293, :234)
-    const double L = tau + dsum * prm.inv_k;   // lower-tail mean
-    const double g_cvar = r - prm.delta - L;
-    double g_star = kSentinel, g_tilde = kSentinel - r;
-    if (prm.epsilon >= 0.0) {  // else: DR LP unbounded (lambda -> inf), solver-failure sentinel
-      g_star = r - prm.delta + prm.eps_over_alpha - L;
-      g_tilde = g_star - r;
-    }
-    store_record(rec, mux, muy, prm.rc, h0, h1, g_cvar, g_star, g_tilde);
+    store_record(rec, mux, muy, prm.rc, h0, h1, offsets_from_tail(prm, r, tau, dsum));
     if (status) status[row] = failure_status(false, prm);
   }
 }

@@ -1,7 +1,9 @@
 // drcvar_selection.inc — the selection toolkit of the halfspace kernels: the launch-uniform Params
 // and their host side (normal_quantile, make_params, params_ok), the wave and workgroup reductions,
 // the bucket map, the histogram scan and the candidate ranking that give the exact order statistic,
-// and the small per-unit formulas (direction, mean halfspace, |h|, status word).  Included inside
+// the exact fallback built from them (select_exact, over a memory or a register source of the
+// unit's projections), and the small per-unit formulas (direction, mean halfspace, |h|, the offsets
+// and the solver-failure offsets, status word).  Included inside
 // the anonymous namespace of drcvar_halfspace.hip (samples read from memory) and
 // drcvar_sampled.hip (samples drawn in the kernel), after <hip/hip_runtime.h>, <cmath>, <cstdint>
 // and drcvar_halfspace.h.  It includes nothing itself — in particular not drcvar_generator.inc:
@@ -10,6 +12,7 @@
 constexpr int kWave = 64;
 constexpr int kCap = 128;          // candidates ranked directly (per-wave region size in LDS)
 constexpr int kMaxValueIters = 3;  // value-linear refinements before switching to integer keys
+constexpr double kSentinel = 100.0;  // the reference's offset for a failed solve
 
 // Launch-uniform scalars, precomputed on the host so the per-unit critical path carries as few
 // fp64 divisions as possible.
@@ -394,6 +397,36 @@ __device__ __forceinline__ void append_candidate_masked(double* region, uint32_t
 // see) included: ahead of the barrier that publishes what they wrote.
 __device__ __forceinline__ void lds_masked_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
+// One lane's tally of the express ranking against its own candidate `mine`: #{z < mine},
+// #{z == mine} and sum_{z < mine} (z - mine) over the candidates z visited so far.
+struct RankTally {
+  uint32_t less = 0u, eq = 0u;
+  double sl = 0.0;
+};
+
+// One visit of the express ranking: the candidate of the lowest lane left in the ballot `m` (taken
+// in scalar code, m != 0) leaves the ballot and enters every lane's tally.
+__device__ __forceinline__ void visit_candidate(double mine, unsigned long long& m, RankTally& t) {
+  const int src = __builtin_ctzll(m);
+  m &= m - 1ull;
+  const double z = readlane_f64(mine, src);
+  const bool lt = z < mine;
+  t.less += lt ? 1u : 0u;
+  t.eq += (z == mine) ? 1u : 0u;
+  t.sl += lt ? z - mine : 0.0;
+}
+
+// The end of the express ranking: tau is the candidate of the first valid lane whose tally places
+// rank rr on it, and that lane holds s_cand itself, so no reduction follows the ranking.
+__device__ __forceinline__ double ranked_candidate(double mine, bool valid, const RankTally& t,
+                                                   uint32_t rr, double* s_cand) {
+  const bool found = valid && t.less <= rr && rr < t.less + t.eq;
+  const unsigned long long fb = __ballot(found);
+  const int src = __ffsll(static_cast<long long>(fb)) - 1;
+  *s_cand = readlane_f64(t.sl, src);
+  return readlane_f64(mine, src);
+}
+
 // Wave 0 (all lanes active), a target bucket of c <= 64 / NW candidates: no wave holds more than
 // E = 64 / NW of them, so wave w appends its candidates to the segment cand[w * E + k] and all of
 // the unit's candidates lie in cand[0 .. 64), in rank_candidates' order (wave, then position)
@@ -409,30 +442,17 @@ __device__ __forceinline__ double rank_candidates_express(double mine, uint32_t 
   constexpr int E = kWave / NW;
   const bool valid = static_cast<uint32_t>(lane & (E - 1)) < cnt;
   unsigned long long m = __ballot(valid);
-  uint32_t less = 0u, eq = 0u;
-  double sl = 0.0;
-  while (m != 0ull) {  // uniform
-    const int src = __builtin_ctzll(m);
-    m &= m - 1ull;
-    const double z = readlane_f64(mine, src);
-    const bool lt = z < mine;
-    less += lt ? 1u : 0u;
-    eq += (z == mine) ? 1u : 0u;
-    sl += lt ? z - mine : 0.0;
-  }
-  const bool found = valid && less <= rr && rr < less + eq;
-  const unsigned long long fb = __ballot(found);
-  const int src = __ffsll(static_cast<long long>(fb)) - 1;
-  *s_cand = readlane_f64(sl, src);
-  return readlane_f64(mine, src);
+  RankTally t;
+  while (m != 0ull) visit_candidate(mine, m, t);  // uniform
+  return ranked_candidate(mine, valid, t, rr, s_cand);
 }
 
 // rank_candidates_express with the tail's wave sum (*s_below = the sum of `tail` over the wave, by
 // wave_reduce's tree) in the same basic block as the ranking's first candidate: the bucket of this
 // path holds at least one, so the first visit is straight-line code whose readlanes and compares
 // fill the wait states of the reduction's DPP stages; the loop takes the remaining candidates (the
-// usual bucket has none: its exit is the fall-through).  The same operations on the same values in
-// the same order as rank_candidates_express: tau and s_cand are bitwise the same.
+// usual bucket has none: its exit is the fall-through).  The visits and the end are
+// rank_candidates_express's own: tau and s_cand are bitwise the same.
 template <int NW>
 __device__ __forceinline__ double rank_candidates_express_tail(double mine, uint32_t cnt,
                                                                uint32_t rr, int lane, double tail,
@@ -440,34 +460,15 @@ __device__ __forceinline__ double rank_candidates_express_tail(double mine, uint
   constexpr int E = kWave / NW;
   const bool valid = static_cast<uint32_t>(lane & (E - 1)) < cnt;
   unsigned long long m = __ballot(valid);
-  uint32_t less = 0u, eq = 0u;
-  double sl = 0.0;
-  {  // the first candidate (m != 0 on this path)
-    const int src = __builtin_ctzll(m);
-    m &= m - 1ull;
-    const double z = readlane_f64(mine, src);
-    const bool lt = z < mine;
-    less += lt ? 1u : 0u;
-    eq += (z == mine) ? 1u : 0u;
-    sl += lt ? z - mine : 0.0;
-  }
+  RankTally t;
+  visit_candidate(mine, m, t);  // the first candidate (m != 0 on this path)
   *s_below = wave_reduce<OpAdd>(tail);
   if (m != 0ull) [[unlikely]] {
     do {  // uniform
-      const int src = __builtin_ctzll(m);
-      m &= m - 1ull;
-      const double z = readlane_f64(mine, src);
-      const bool lt = z < mine;
-      less += lt ? 1u : 0u;
-      eq += (z == mine) ? 1u : 0u;
-      sl += lt ? z - mine : 0.0;
+      visit_candidate(mine, m, t);
     } while (m != 0ull);
   }
-  const bool found = valid && less <= rr && rr < less + eq;
-  const unsigned long long fb = __ballot(found);
-  const int src = __ffsll(static_cast<long long>(fb)) - 1;
-  *s_cand = readlane_f64(sl, src);
-  return readlane_f64(mine, src);
+  return ranked_candidate(mine, valid, t, rr, s_cand);
 }
 
 // Wave 0 (all lanes active): tau = the candidate of rank rr among the c <= kCap candidates held in
@@ -542,6 +543,151 @@ __device__ __forceinline__ double rank_candidates(const double* cand, uint32_t c
                                            : rank_candidates_q<NW, 2>(cand, cw, c, rr, lane, s_cand);
 }
 
+// ---------------------------------------------------------------------------------------------
+// the exact fallback
+// ---------------------------------------------------------------------------------------------
+// A source hands select_exact the projections d_i of one unit, this thread's share of them, through
+// two visitors: each_sample(f) calls f(d) for the samples this thread holds (any trip count), and
+// each_slot(f) calls f(d) the same number of times in every thread of the workgroup, with NaN for a
+// slot that holds no sample (never in range, never below: ballots see whole waves).
+//
+// The unit's samples in memory, re-read (L2/MALL-hot) on every pass: thread `tid` holds samples
+// tid, tid + BLOCK, ...; proj(i) is the projection h . xi_i of sample i.
+template <int BLOCK, class Proj>
+struct MemorySource {
+  const Proj& proj;
+  int n;
+  template <class F>
+  __device__ __forceinline__ void each_sample(F&& f) const {
+    for (int i = threadIdx.x; i < n; i += BLOCK) f(proj(i));
+  }
+  template <class F>
+  __device__ __forceinline__ void each_slot(F&& f) const {
+    for (int i0 = 0; i0 < n; i0 += BLOCK) {  // uniform trip count
+      const int i = i0 + static_cast<int>(threadIdx.x);
+      f(i < n ? proj(i) : NAN);
+    }
+  }
+};
+template <int BLOCK, class Proj>
+__device__ __forceinline__ MemorySource<BLOCK, Proj> memory_source(const Proj& proj, int n) {
+  return MemorySource<BLOCK, Proj>{proj, n};
+}
+
+// The unit's projections held in registers: d[0..Q), bit q of vmask set where slot q holds a
+// sample.  Nothing is re-read; an idle slot is NaN to both visitors.
+template <int Q>
+struct RegisterSource {
+  const double (&d)[Q];
+  uint32_t vmask;
+  template <class F>
+  __device__ __forceinline__ void each_slot(F&& f) const {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) f(((vmask >> q) & 1u) ? d[q] : NAN);
+  }
+  template <class F>
+  __device__ __forceinline__ void each_sample(F&& f) const {
+    each_slot(f);
+  }
+};
+
+// Exact selection for the units the window fast path does not finish (a target outside the window,
+// degenerate moments, or a first-pass bucket with more than kCap samples): exact min/max of the
+// source's projections, then histogram refinement (value-linear, then order-preserving integer
+// keys) until <= kCap candidates remain or the run collapses to one value.  Begins with a barrier
+// (the fast path's readers of hist / red_* are done); every wave returns; the result is valid in
+// wave 0: tau and dsum = sum_{d<tau} (d - tau).
+template <int BLOCK, int LOG_NB, class Source>
+__device__ __forceinline__ void select_exact(const Source& src, double mu_d, uint32_t rank,
+                                             uint32_t* hist, double* cand, uint32_t* wcount,
+                                             double* red_rng, double* red_tail, double* tau_out,
+                                             double* dsum_out) {
+  constexpr int NW = BLOCK / kWave;
+  constexpr int NB = 1 << LOG_NB;
+  const int tid = threadIdx.x;
+  const int lane = tid & (kWave - 1);
+  const int wave = tid / kWave;
+  __syncthreads();
+
+  double vmin[1] = {INFINITY}, vmax[1] = {-INFINITY};
+  src.each_sample([&](double v) {
+    vmin[0] = fmin(vmin[0], v);
+    vmax[0] = fmax(vmax[0], v);
+  });
+  block_reduce<OpMin, NW, 1>(vmin, red_rng);
+  block_reduce<OpMax, NW, 1>(vmax, red_rng + NW);
+  double lo = vmin[0], hi = vmax[0];
+  if (lo == hi) {  // every sample projects to one value (the noise-free step 0): no tail below it
+    *tau_out = lo;
+    *dsum_out = 0.0;
+    return;        // uniform; no second pass over the samples
+  }
+  uint32_t rr = rank, c = 0;
+  bool have_bin = false, tau_known = false;
+  double tau = lo;
+  int bin = 0;
+  BucketMap<LOG_NB> map;
+  for (int iter = 0; !tau_known; ++iter) {
+    map.init_range(lo, hi, iter);
+    for (int b = tid; b < hist_words<NB>(); b += BLOCK) hist[b] = 0u;
+    __syncthreads();
+    src.each_sample([&](double v) {
+      if (in_range(v, lo, hi)) atomicAdd(&hist[hist_slot<NB>(map(v))], 1u);
+    });
+    __syncthreads();
+    const ScanResult sr = scan_bins<NB>(hist, rr, lane);
+    bin = sr.bin;
+    rr -= sr.below;
+    c = sr.cnt;
+    have_bin = true;
+    if (c <= kCap) break;
+    double rmin[1] = {INFINITY}, rmax[1] = {-INFINITY};
+    src.each_sample([&](double v) {
+      if (in_range(v, lo, hi) && map(v) == bin) {
+        rmin[0] = fmin(rmin[0], v);
+        rmax[0] = fmax(rmax[0], v);
+      }
+    });
+    __syncthreads();  // all waves have scanned hist before it is cleared again
+    block_reduce<OpMin, NW, 1>(rmin, red_rng);
+    block_reduce<OpMax, NW, 1>(rmax, red_rng + NW);
+    lo = rmin[0];
+    hi = rmax[0];
+    have_bin = false;
+    if (lo == hi) {
+      tau_known = true;
+      tau = lo;
+    }
+  }
+
+  double sq = 0.0;
+  uint32_t wbase = 0;
+  const unsigned long long lt_mask = (1ull << lane) - 1ull;
+  src.each_slot([&](double v) {
+    const bool inr = in_range(v, lo, hi);
+    const int bj = (have_bin && inr) ? map(v) : 0;
+    const bool below = v < lo || (have_bin && inr && bj < bin);
+    if (below) sq += v - mu_d;
+    append_candidate(cand + wave * kCap, wbase, !tau_known && inr && (!have_bin || bj == bin), v,
+                     lt_mask);
+  });
+  sq = wave_reduce<OpAdd>(sq);
+  if (lane == 0) {
+    red_tail[wave] = sq;
+    wcount[wave] = wbase;
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const double s_below = sum_partials<NW>(red_tail);
+  double s_cand = 0.0;
+  // lane w < NW: the candidate count of wave w (0 elsewhere)
+  if (!tau_known)
+    tau = rank_candidates<NW>(cand, lane < NW ? wcount[lane] : 0u, c, rr, lane, &s_cand);
+  const double n_below = static_cast<double>(rank - rr);
+  *tau_out = tau;
+  *dsum_out = (s_below - n_below * (tau - mu_d)) + s_cand;
+}
+
 // compute_separating_vector(ego, mu) (core/geometry.py:35-53): (mu - ego) / |mu - ego|, [1, 0]
 // below 1e-10.  RSQRT is the kernel's reciprocal square root — rsqrt_nr for the stored form,
 // rsqrt_nr2 for the sampled one: the two give different bits of h on purpose, and each kernel's
@@ -575,6 +721,27 @@ __device__ __forceinline__ double norm_h(double h0, double h1) {
 __device__ __forceinline__ int32_t failure_status(bool nonfinite, const Params& prm) {
   return (nonfinite ? DRCVAR_UNIT_NONFINITE : 0) | (prm.unbounded ? DRCVAR_UNIT_UNBOUNDED : 0) |
          (prm.epsilon < 0.0 ? DRCVAR_UNIT_DR_UNBOUNDED : 0);
+}
+
+// Columns 5..7 of the record from the lower-tail statistics: L = tau + dsum / k is the lower-tail
+// mean, r = R_c |h| (risk_metrics.py:293, :234).
+struct Offsets {
+  double g_cvar, g_star, g_tilde;
+};
+__device__ __forceinline__ Offsets offsets_from_tail(const Params& prm, double r, double tau,
+                                                     double dsum) {
+  const double L = tau + dsum * prm.inv_k;
+  Offsets g{r - prm.delta - L, kSentinel, kSentinel - r};
+  if (prm.epsilon >= 0.0) {  // else: DR LP unbounded (lambda -> inf), solver-failure sentinel
+    g.g_star = r - prm.delta + prm.eps_over_alpha - L;
+    g.g_tilde = g.g_star - r;
+  }
+  return g;
+}
+// ... and of a unit whose solve failed (risk_metrics.py:298-303,334-338); its status word is
+// failure_status's.
+__device__ __forceinline__ Offsets failure_offsets(double r) {
+  return Offsets{kSentinel, kSentinel, kSentinel - r};
 }
 
 // ---------------------------------------------------------------------------------------------

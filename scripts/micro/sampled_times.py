@@ -25,6 +25,9 @@ import torch
 
 REPO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "scripts"))
+import diaglib  # noqa: E402
+diaglib.apply()  # DRCVAR_DIAG_LIB: a variant build (diagnostics)
 
 from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd import _native, engine, synthetic  # noqa: E402
 from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd.engine import RiskParams  # noqa: E402

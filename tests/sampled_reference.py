@@ -16,7 +16,8 @@ form's ``z_lo``, ``window_sd`` (``halfspace_reference.window_params``) and the p
 * ``CROWDED``   tau's bucket holds more than 128 samples;
 * ``NOWINDOW``  sd_d is not positive or not finite (a zero or overflowing factor).
 
-All but SETTLED and FAST enter the kernel's exact fallback over its registers.  A class is reported
+All but SETTLED and FAST enter the exact fallback (select_exact of csrc/drcvar_selection.inc, the
+stored form's own routine) over the kernel's registers.  A class is reported
 only when it is the same with sd_d scaled by 0.99, 1 and 1.01; otherwise ``UNSURE``.  The mirror
 works in long double on the stored samples.  Where every sample of a noisy unit is the same point
 (noise below one ulp of the position, sd_d > 0) it has d - mu_d = 0 exactly, and the class follows

@@ -137,7 +137,7 @@ def test_case_table_reaches_every_path_class(geo):
     families built to leave the fast path are predicted to: crowd_tau where it holds more than
     128 ties (N >= 172), geometric where N >= 256 and tau is not the isolated maximum, head_equal
     where the equal head is the kernel's whole subsample (N >= 2 heads).  (The streaming kernel has
-    no window: every unit goes through the refinement of select_from_memory.)"""
+    no window: every unit goes through the refinement of select_exact.)"""
     block, per, log_nb = geo
     head = hr.head_of(block, per)
     reached = {c: [] for c in CLASSES}
