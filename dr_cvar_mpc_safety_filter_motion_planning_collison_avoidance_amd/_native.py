@@ -27,6 +27,12 @@ INCLUDE_DIR = os.path.join(REPO_DIR, "include")
 HEADERS = [os.path.join(INCLUDE_DIR, h) for h in ("drcvar_halfspace.h", "drcvar_mpc.h",
                                                   "drcvar_sampling.h", "drcvar_exchange.h")]
 OFFLOAD_ARCH = "gfx950"  # CDNA4 only
+# The loop library (include/drcvar_loop.h): csrc/drcvar_step.hip compiled once more, with
+# DRCVAR_LOOP_LIBRARY, into a library of its own, so that the engine library exports what it did.
+LOOP_LIB_PATH = os.path.join(LIB_DIR, "libdrcvar_loop.so")
+LOOP_HEADER = os.path.join(INCLUDE_DIR, "drcvar_loop.h")
+LOOP_UNIT = (os.path.join(PKG_DIR, "csrc", "drcvar_step.hip"), ("-DDRCVAR_LOOP_LIBRARY",))
+LOOP_SYMBOLS = ("drcvar_mpc_step_advance_batch_f64",)   # every symbol drcvar_loop.h declares
 
 ABI_VERSION = 3
 OUT_WIDTH = 8
@@ -253,11 +259,11 @@ def build(verbose: bool = False, extra_flags=()) -> str:
     os.makedirs(obj_dir, exist_ok=True)
     import glob
     incs = sorted(glob.glob(os.path.join(PKG_DIR, "csrc", "*.inc")))  # tables the sources include
-    headers = b"".join(open(h, "rb").read() for h in HEADERS + incs)
+    headers = b"".join(open(h, "rb").read() for h in HEADERS + [LOOP_HEADER] + incs)
     # the compiler's identity is part of every key: objects of an older hipcc / ROCm are rebuilt
     toolchain = _toolchain(probe=True)
     objs, procs = [], []
-    for src, defs in _compile_units():
+    for src, defs in _compile_units() + [LOOP_UNIT]:
         flags = _unit_flags(defs, extra_flags)
         key = hashlib.sha256(open(src, "rb").read() + headers + toolchain
                              + " ".join(flags).encode()).hexdigest()[:16]
@@ -275,12 +281,13 @@ def build(verbose: bool = False, extra_flags=()) -> str:
         raise subprocess.CalledProcessError(1, failed[0])
     for _, obj, _ in procs:
         os.replace(obj + ".tmp", obj)
-    link = ["hipcc", f"--offload-arch={OFFLOAD_ARCH}", "-shared", "-fPIC", *objs,
-            "-o", LIB_PATH + ".tmp"]
-    if verbose:
-        print(" ".join(link))
-    subprocess.run(link, check=True)
-    os.replace(LIB_PATH + ".tmp", LIB_PATH)
+    for path, members in ((LIB_PATH, objs[:-1]), (LOOP_LIB_PATH, objs[-1:])):   # (LOOP_UNIT is last)
+        link = ["hipcc", f"--offload-arch={OFFLOAD_ARCH}", "-shared", "-fPIC", *members,
+                "-o", path + ".tmp"]
+        if verbose:
+            print(" ".join(link))
+        subprocess.run(link, check=True)
+        os.replace(path + ".tmp", path)
     keep = set(objs)  # drop stale cached objects (not *.tmp: another build may be writing them)
     for f in os.listdir(obj_dir):
         if f.endswith(".o") and os.path.join(obj_dir, f) not in keep:
@@ -404,6 +411,33 @@ def lib():
                 raise NativeLibraryError("engine ABI version mismatch; rebuild the library")
             _lib = handle
     return _lib
+
+
+_loop_lib = None
+
+
+def loop_lib():
+    """The loaded loop library (``include/drcvar_loop.h``; raises NativeLibraryError if it is not
+    built: there is no fallback).  It shares the engine library's structs and return codes."""
+    global _loop_lib
+    if _loop_lib is not None:
+        return _loop_lib
+    with _lock:
+        if _loop_lib is None:
+            if not os.path.exists(LOOP_LIB_PATH):
+                raise NativeLibraryError(
+                    f"loop library not built: {LOOP_LIB_PATH} is missing (run __graft_entry__.build())")
+            try:
+                handle = ctypes.CDLL(LOOP_LIB_PATH)
+            except OSError as exc:  # pragma: no cover - depends on the ROCm install
+                raise NativeLibraryError(f"cannot load {LOOP_LIB_PATH}: {exc}") from exc
+            i64, ptr = ctypes.c_int64, ctypes.c_void_p
+            handle.drcvar_mpc_step_advance_batch_f64.argtypes = [
+                ctypes.POINTER(MpcModel), i64, ptr, ptr, ptr, ptr, ptr, i64, ptr, i64, i64, ptr, ptr,
+                ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
+            handle.drcvar_mpc_step_advance_batch_f64.restype = ctypes.c_int
+            _loop_lib = handle
+    return _loop_lib
 
 
 def check(code: int) -> None:

@@ -1,5 +1,9 @@
 // drcvar_step.hip — the advance kernel of the receding-horizon loop, for gfx950: one small launch
-// that closes a control step of one problem (include/drcvar_mpc.h, drcvar_mpc_step_advance_f64).
+// that closes a control step of one problem (include/drcvar_mpc.h, drcvar_mpc_step_advance_f64) or
+// of n_problems problems advancing in lockstep (include/drcvar_loop.h,
+// drcvar_mpc_step_advance_batch_f64).  The source is compiled twice, same kernel: into the engine
+// library with the single entry, and with DRCVAR_LOOP_LIBRARY into the loop library with the batch
+// entry (the engine library's symbol list stays what it was).
 //
 // Reference: the caller's loop around MPCSafetyFilter.filter_trajectory, once per control step
 // (core/mpc_filter.py:40-178): apply the first input, remember the optimum on a solved call
@@ -8,7 +12,10 @@
 // drcvar_sampled.hip), the QP (drcvar_mpc.hip), this kernel — that a graph captures once: every
 // quantity that changes from step to step lives in device memory and is rewritten here.
 //
-// One workgroup of kThreads threads; thread e owns element e of the [H, nu] input arrays
+// One workgroup of kThreads threads per problem (blockIdx.x = b; the single entry launches one);
+// workgroup b works on problem b's slices of every per-problem buffer and on state[b] alone, so no
+// workgroup reads what another writes and the launch needs no atomics and no ordering between
+// workgroups.  Thread e owns element e of the [H, nu] input arrays
 // (H nu <= DRCVAR_MPC_MAX_HORIZON DRCVAR_MPC_MAX_INPUTS = kThreads).  Everything a later store of
 // this launch could overwrite (state, have_last, last_u) is read into registers first, then one
 // barrier, then the stores: the order of the header's steps 1-7 is the order of the values, and no
@@ -19,12 +26,14 @@
 
 #include <cstdint>
 
+#include "drcvar_loop.h"
 #include "drcvar_mpc.h"
 
 namespace {
 
 constexpr int kThreads = DRCVAR_MPC_MAX_HORIZON * DRCVAR_MPC_MAX_INPUTS;  // 256
 
+// (the per-problem pointers: problem 0's slice; problem b's follows from the dense batch shapes)
 struct StepArgs {
   const double* x_out;
   const double* u_out;
@@ -54,6 +63,23 @@ __device__ __forceinline__ int64_t path_row(int64_t base, int64_t k, int64_t las
 __global__ void __launch_bounds__(kThreads) step_advance_kernel(StepArgs a) {
   const int e = threadIdx.x;
   const int H = a.H, nx = a.nx, nu = a.nu;
+  const int n_u = H * nu, n_w = (H + 1) * nx;
+  {  // problem b's slices (uniform over the workgroup: scalar arithmetic)
+    const int64_t b = blockIdx.x;
+    a.x_out += b * n_w;
+    a.u_out += b * n_u;
+    a.info += b * DRCVAR_MPC_INFO_WIDTH;
+    if (a.disturbance) a.disturbance += b * a.log_rows * nx;
+    a.x_log += b * (a.log_rows + 1) * nx;
+    a.u_log += b * a.log_rows * nu;
+    a.info_log += b * a.log_rows * DRCVAR_MPC_INFO_WIDTH;
+    a.x0 += b * nx;
+    a.x_ref_win += b * n_w;
+    a.u_fallback += b * n_u;
+    a.last_u += b * n_u;
+    a.have_last += b;
+    a.state += b;
+  }
   // ---- reads (before the barrier) ----------------------------------------------------------
   const int64_t s = a.state->step;
   const uint64_t words = a.state->stream_offset;
@@ -68,7 +94,6 @@ __global__ void __launch_bounds__(kThreads) step_advance_kernel(StepArgs a) {
   const bool solved = st == static_cast<double>(DRCVAR_MPC_STATUS_OPTIMAL) ||
                       st == static_cast<double>(DRCVAR_MPC_STATUS_OPTIMAL_INACCURATE);
   const bool have = solved || *a.have_last != 0;
-  const int n_u = H * nu;
   double keep = 0.0, next_fb = 0.0;  // last_u[e] and u_fallback[e] after this step
   if (e < n_u) {
     const int k = e / nu, j = e - k * nu;
@@ -96,7 +121,7 @@ __global__ void __launch_bounds__(kThreads) step_advance_kernel(StepArgs a) {
     a.u_fallback[e] = next_fb;
   }
   if (e < nx) a.x0[e] = x_next;
-  for (int q = e; q < (H + 1) * nx; q += kThreads) {
+  for (int q = e; q < n_w; q += kThreads) {
     const int k = q / nx, j = q - k * nx;
     a.x_ref_win[q] = a.x_ref_path[path_row(base, k, a.path_last) * nx + j];
   }
@@ -107,14 +132,14 @@ __global__ void __launch_bounds__(kThreads) step_advance_kernel(StepArgs a) {
   }
 }
 
-}  // namespace
-
-extern "C" int drcvar_mpc_step_advance_f64(
-    const drcvar_mpc_model* model, const double* x_out, const double* u_out, const double* info,
-    const double* x_ref_path, const double* u_ref_path, int64_t path_steps,
-    const double* disturbance, int64_t step_begin, int64_t log_rows, double* x_log, double* u_log,
-    double* info_log, double* x0, double* x_ref_win, double* u_fallback, double* last_u,
-    int32_t* have_last, drcvar_step_state* state, void* stream) {
+// the checks both entries share, then one launch of n_problems workgroups
+int launch_step_advance(const drcvar_mpc_model* model, int64_t n_problems, const double* x_out,
+                        const double* u_out, const double* info, const double* x_ref_path,
+                        const double* u_ref_path, int64_t path_steps, const double* disturbance,
+                        int64_t step_begin, int64_t log_rows, double* x_log, double* u_log,
+                        double* info_log, double* x0, double* x_ref_win, double* u_fallback,
+                        double* last_u, int32_t* have_last, drcvar_step_state* state,
+                        void* stream) {
   if (!model || !x_out || !u_out || !info || !x_ref_path || !u_ref_path || !x_log || !u_log ||
       !info_log || !x0 || !x_ref_win || !u_fallback || !last_u || !have_last || !state)
     return DRCVAR_ERR_INVALID_ARGUMENT;
@@ -124,6 +149,7 @@ extern "C" int drcvar_mpc_step_advance_f64(
       model->n_states > DRCVAR_MPC_MAX_STATES || model->n_inputs < 1 ||
       model->n_inputs > DRCVAR_MPC_MAX_INPUTS)
     return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (n_problems > INT32_MAX) return DRCVAR_ERR_UNSUPPORTED;  // one workgroup each: the grid's limit
   StepArgs a{};
   a.x_out = x_out;
   a.u_out = u_out;
@@ -147,7 +173,35 @@ extern "C" int drcvar_mpc_step_advance_f64(
   a.nx = model->n_states;
   a.nu = model->n_inputs;
   (void)hipGetLastError();  // clear stale errors from unrelated work
-  hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(kThreads), 0,
-                     static_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(step_advance_kernel, dim3(static_cast<unsigned>(n_problems)), dim3(kThreads),
+                     0, static_cast<hipStream_t>(stream), a);
   return hipGetLastError() == hipSuccess ? DRCVAR_OK : DRCVAR_ERR_LAUNCH;
 }
+
+}  // namespace
+
+#ifndef DRCVAR_LOOP_LIBRARY
+extern "C" int drcvar_mpc_step_advance_f64(
+    const drcvar_mpc_model* model, const double* x_out, const double* u_out, const double* info,
+    const double* x_ref_path, const double* u_ref_path, int64_t path_steps,
+    const double* disturbance, int64_t step_begin, int64_t log_rows, double* x_log, double* u_log,
+    double* info_log, double* x0, double* x_ref_win, double* u_fallback, double* last_u,
+    int32_t* have_last, drcvar_step_state* state, void* stream) {
+  return launch_step_advance(model, 1, x_out, u_out, info, x_ref_path, u_ref_path, path_steps,
+                             disturbance, step_begin, log_rows, x_log, u_log, info_log, x0,
+                             x_ref_win, u_fallback, last_u, have_last, state, stream);
+}
+#else
+extern "C" int drcvar_mpc_step_advance_batch_f64(
+    const drcvar_mpc_model* model, int64_t n_problems, const double* x_out, const double* u_out,
+    const double* info, const double* x_ref_path, const double* u_ref_path, int64_t path_steps,
+    const double* disturbance, int64_t step_begin, int64_t log_rows, double* x_log, double* u_log,
+    double* info_log, double* x0, double* x_ref_win, double* u_fallback, double* last_u,
+    int32_t* have_last, drcvar_step_state* state, void* stream) {
+  if (n_problems < 0) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (n_problems == 0) return DRCVAR_OK;  // nothing to do: no launch, no pointer is looked at
+  return launch_step_advance(model, n_problems, x_out, u_out, info, x_ref_path, u_ref_path,
+                             path_steps, disturbance, step_begin, log_rows, x_log, u_log, info_log,
+                             x0, x_ref_win, u_fallback, last_u, have_last, state, stream);
+}
+#endif
