@@ -1,6 +1,7 @@
 """Loader for the HIP engine (``_lib/libdrcvar_halfspace.so``) — the C ABI of
 ``include/drcvar_halfspace.h`` (+ ``drcvar_mpc.h``, ``drcvar_sampling.h``, ``drcvar_exchange.h``)
-bound with ctypes.
+bound with ctypes; beside it the loop library (``drcvar_loop.h``, :func:`loop_lib`) and the
+loop-evaluation library (``drcvar_loop_eval.h``, :func:`eval_lib`), one entry family each.
 
 There is deliberately no fallback: if the shared library is missing or cannot be loaded every
 entry point raises :class:`NativeLibraryError`.  ``build()`` compiles it for gfx950 in-tree.
@@ -33,6 +34,12 @@ LOOP_LIB_PATH = os.path.join(LIB_DIR, "libdrcvar_loop.so")
 LOOP_HEADER = os.path.join(INCLUDE_DIR, "drcvar_loop.h")
 LOOP_UNIT = (os.path.join(PKG_DIR, "csrc", "drcvar_step.hip"), ("-DDRCVAR_LOOP_LIBRARY",))
 LOOP_SYMBOLS = ("drcvar_mpc_step_advance_batch_f64",)   # every symbol drcvar_loop.h declares
+# The loop-evaluation library (include/drcvar_loop_eval.h), by the same recipe:
+# csrc/drcvar_clearance.hip compiled once more, with DRCVAR_LOOP_EVAL_LIBRARY.
+EVAL_LIB_PATH = os.path.join(LIB_DIR, "libdrcvar_loop_eval.so")
+EVAL_HEADER = os.path.join(INCLUDE_DIR, "drcvar_loop_eval.h")
+EVAL_UNIT = (os.path.join(PKG_DIR, "csrc", "drcvar_clearance.hip"), ("-DDRCVAR_LOOP_EVAL_LIBRARY",))
+EVAL_SYMBOLS = ("drcvar_loop_clearance_f64", "drcvar_loop_clearance_f64_ex")
 
 ABI_VERSION = 3
 OUT_WIDTH = 8
@@ -259,11 +266,11 @@ def build(verbose: bool = False, extra_flags=()) -> str:
     os.makedirs(obj_dir, exist_ok=True)
     import glob
     incs = sorted(glob.glob(os.path.join(PKG_DIR, "csrc", "*.inc")))  # tables the sources include
-    headers = b"".join(open(h, "rb").read() for h in HEADERS + [LOOP_HEADER] + incs)
+    headers = b"".join(open(h, "rb").read() for h in HEADERS + [LOOP_HEADER, EVAL_HEADER] + incs)
     # the compiler's identity is part of every key: objects of an older hipcc / ROCm are rebuilt
     toolchain = _toolchain(probe=True)
     objs, procs = [], []
-    for src, defs in _compile_units() + [LOOP_UNIT]:
+    for src, defs in _compile_units() + [LOOP_UNIT, EVAL_UNIT]:
         flags = _unit_flags(defs, extra_flags)
         key = hashlib.sha256(open(src, "rb").read() + headers + toolchain
                              + " ".join(flags).encode()).hexdigest()[:16]
@@ -281,7 +288,9 @@ def build(verbose: bool = False, extra_flags=()) -> str:
         raise subprocess.CalledProcessError(1, failed[0])
     for _, obj, _ in procs:
         os.replace(obj + ".tmp", obj)
-    for path, members in ((LIB_PATH, objs[:-1]), (LOOP_LIB_PATH, objs[-1:])):   # (LOOP_UNIT is last)
+    # (LOOP_UNIT and EVAL_UNIT are the last two: each is a library of its own)
+    for path, members in ((LIB_PATH, objs[:-2]), (LOOP_LIB_PATH, objs[-2:-1]),
+                          (EVAL_LIB_PATH, objs[-1:])):
         link = ["hipcc", f"--offload-arch={OFFLOAD_ARCH}", "-shared", "-fPIC", *members,
                 "-o", path + ".tmp"]
         if verbose:
@@ -438,6 +447,39 @@ def loop_lib():
             handle.drcvar_mpc_step_advance_batch_f64.restype = ctypes.c_int
             _loop_lib = handle
     return _loop_lib
+
+
+_eval_lib = None
+
+
+def eval_lib():
+    """The loaded loop-evaluation library (``include/drcvar_loop_eval.h``; raises
+    NativeLibraryError if it is not built: there is no fallback).  It shares the engine library's
+    structs and return codes."""
+    global _eval_lib
+    if _eval_lib is not None:
+        return _eval_lib
+    with _lock:
+        if _eval_lib is None:
+            if not os.path.exists(EVAL_LIB_PATH):
+                raise NativeLibraryError(
+                    f"loop-evaluation library not built: {EVAL_LIB_PATH} is missing (run "
+                    f"__graft_entry__.build())")
+            try:
+                handle = ctypes.CDLL(EVAL_LIB_PATH)
+            except OSError as exc:  # pragma: no cover - depends on the ROCm install
+                raise NativeLibraryError(f"cannot load {EVAL_LIB_PATH}: {exc}") from exc
+            i64, i32, dbl, u64, ptr = (ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                                       ctypes.c_uint64, ctypes.c_void_p)
+            handle.drcvar_loop_clearance_f64.argtypes = [
+                i64, ptr, i32, ptr, ptr, i64, i64, i64, i64, ptr, i64, i64, i64, i32, dbl, dbl, dbl,
+                dbl, i64, u64, u64, u64, i32, ptr, i64, ptr, ptr]
+            handle.drcvar_loop_clearance_f64.restype = ctypes.c_int
+            handle.drcvar_loop_clearance_f64_ex.argtypes = \
+                handle.drcvar_loop_clearance_f64.argtypes[:-1] + [i32, ptr]
+            handle.drcvar_loop_clearance_f64_ex.restype = ctypes.c_int
+            _eval_lib = handle
+    return _eval_lib
 
 
 def check(code: int) -> None:

@@ -23,6 +23,14 @@
 // (the order of non-negative doubles is the order of their bit patterns: exact, independent of
 // arrival order), and a finishing launch applies sqrt - R in place.  One split stores directly.
 // Both paths take the minimum of the same d^2 values and apply the same sqrt: the same bits.
+//
+// The source is compiled twice.  Into the engine library: the kernel above behind
+// drcvar_min_clearance_f64[_ex].  With DRCVAR_LOOP_EVAL_LIBRARY into a library of its own
+// (include/drcvar_loop_eval.h): the device-state, batched, one-row form for receding-horizon
+// loops replayed from a graph (loop_clearance_kernel below).  Both draw with draw_noise and form
+// the obstacle point and d^2 by the same expressions.  (A shared inline helper for those four lines
+// changed the first kernel's instruction schedule; as written the engine unit's code is the
+// instruction stream it was before the second form existed.)
 
 #include <hip/hip_runtime.h>
 
@@ -33,6 +41,9 @@
 #include <limits>
 
 #include "drcvar_sampling.h"
+#ifdef DRCVAR_LOOP_EVAL_LIBRARY
+#include "drcvar_loop_eval.h"
+#endif
 
 namespace {
 
@@ -59,8 +70,9 @@ struct ClearArgs {
 // The noise of one (m, o, t) from its Philox call.  kLaplace: the log carries lam = 1/2, so
 // scaled_neg2_log_u32 is E = -log u; otherwise lam = 1 and (x0, x1) are Box-Muller's radius and
 // angle words (x2, x3 unused).
-template <bool kLaplace>
-__device__ __forceinline__ void draw_noise(uint64_t g, const ClearArgs& a, const double* s_turn,
+// Args: a kernel's argument struct with p0, p1, p2, pu and lg.
+template <bool kLaplace, class Args>
+__device__ __forceinline__ void draw_noise(uint64_t g, const Args& a, const double* s_turn,
                                            const double* s_log, double* nx, double* ny) {
   const Philox r = philox4x32_10(static_cast<uint32_t>(g), static_cast<uint32_t>(g >> 32), a.pu);
   if constexpr (kLaplace) {
@@ -88,6 +100,7 @@ __device__ __forceinline__ double min_f64(double a, double b) {
   return r;
 }
 
+#ifndef DRCVAR_LOOP_EVAL_LIBRARY
 template <int K, bool kLaplace>
 __global__ __launch_bounds__(kBlock) void clearance_kernel(const double* __restrict__ ego,
                                                            const double* __restrict__ nominal,
@@ -184,8 +197,202 @@ void launch_for_k(int K, dim3 grid, hipStream_t s, const double* ego, const doub
   }
 }
 
+#else  // DRCVAR_LOOP_EVAL_LIBRARY: the device-state, batched, one-row form
+
+// One launch evaluates the CURRENT state of each of B loops: O points per (problem, realisation)
+// where the kernel above has O T.  blockIdx.y = problem b, so state[b], x0[b] and the obstacles'
+// nominal row are uniform over the workgroup (scalar loads), and the table load is paid once per
+// workgroup: a thread takes per_thread realisations, kBlock apart (coalesced min_d2 rows), and
+// blockIdx.x picks the chunk of per_thread kBlock realisations.  Exactly one thread owns (b, m) in
+// a launch: the running minimum is a load, a v_min_f64 and a store, ordered against the previous
+// control step's launch by the stream alone.  The hit count of a wave is summed over its
+// realisations in a scalar register (one ballot and popcount each) and leaves as at most one
+// integer atomic add.  Nothing depends on per_thread or the grid but which thread owns (b, m).
+constexpr int kMaxStates = 8;           // DRCVAR_MPC_MAX_STATES
+constexpr int kRulePerThread = 8;       // the most realisations per thread the rule below chooses
+constexpr int kMaxPerThread = 64;       // ... and the most a caller may ask for
+constexpr int64_t kWantedLoopGroups = 2048;  // workgroups before a thread takes more realisations
+
+struct LoopEvalArgs {
+  int64_t nom_so, nom_st, O, Tn, OT, path_last, step_begin, log_rows, M, out_sb;
+  uint64_t eval_offset, offset_stride;
+  uint32_t k0, k1;  // the seed's words
+  int nx, zero_first, per_thread;
+  double cx[kMaxStates], cy[kMaxStates];  // c_out's two rows, zero past nx
+  double p0, p1, p2, RR;
+  LogScale lg;
+};
+
+// what draw_noise takes (ClearArgs' noise members)
+struct NoiseArgs {
+  double p0, p1, p2;
+  PhiloxUniform pu;
+  LogScale lg;
+};
+
+template <bool kLaplace>
+__global__ __launch_bounds__(kBlock) void loop_clearance_kernel(
+    const double* __restrict__ x0, const double* __restrict__ nominal,
+    const drcvar_step_state* __restrict__ state, double* __restrict__ min_d2,
+    unsigned long long* __restrict__ hits, LoopEvalArgs a) {
+  __shared__ double s_turn[kTurnLen], s_log[2 * kLogIdx];
+  const int64_t b = blockIdx.y;
+  const int64_t s = state[b].step;
+  // i = s - step_begin in wrapping arithmetic, as the advance kernel forms it; the state just
+  // reached is log row i, so i = log_rows is still a row
+  const uint64_t i = static_cast<uint64_t>(s) - static_cast<uint64_t>(a.step_begin);
+  if (i > static_cast<uint64_t>(a.log_rows) || s < 0 || s >= a.Tn) return;  // (the whole workgroup)
+  load_generator_tables(s_turn, s_log, kBlock, a.lg.lam);
+  __syncthreads();
+  // ego = c_out x0[b]: an fma chain from +0.0 over the states
+  double ex = 0.0, ey = 0.0;
+  const double* xb = x0 + b * a.nx;
+#pragma unroll
+  for (int j = 0; j < kMaxStates; ++j) {
+    if (j < a.nx) {
+      const double xj = xb[j];
+      ex = fma(a.cx[j], xj, ex);
+      ey = fma(a.cy[j], xj, ey);
+    }
+  }
+  const uint64_t words = a.eval_offset + static_cast<uint64_t>(b) * a.offset_stride;  // mod 2^64
+  NoiseArgs n;
+  n.p0 = a.p0;
+  n.p1 = a.p1;
+  n.p2 = a.p2;
+  n.pu = make_philox_uniform(static_cast<uint32_t>(words), static_cast<uint32_t>(words >> 32), a.k0, a.k1);
+  n.lg = a.lg;
+  const bool noisy = !(a.zero_first && s == 0);  // the noise-free first step: no Philox call
+  const int64_t row = s < a.path_last ? s : a.path_last;
+  const double* nom_b = nominal + b * a.O * a.nom_so + row * a.nom_st;
+  double* out = min_d2 + b * a.out_sb;
+  const int wave_first = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) & ~63);
+  const int64_t chunk = static_cast<int64_t>(blockIdx.x) * a.per_thread * kBlock;
+  const double inf = std::numeric_limits<double>::infinity();
+  unsigned int count = 0;  // this wave's realisations in collision (uniform over the wave)
+  for (int r = 0; r < a.per_thread; ++r) {
+    const int64_t first = chunk + static_cast<int64_t>(r) * kBlock;
+    if (first + wave_first >= a.M) break;  // nothing left for this wave
+    const int64_t m = first + threadIdx.x;
+    const bool valid = m < a.M;
+    // a lane past M draws realisation 0 (no index depends on it) and neither stores nor counts
+    const uint64_t gm = static_cast<uint64_t>(valid ? m : 0) * static_cast<uint64_t>(a.OT);
+    double mo = inf;
+    const double* nom = nom_b;
+    uint64_t ot = static_cast<uint64_t>(s);  // o T_n + s
+    for (int64_t o = 0; o < a.O; ++o, nom += a.nom_so, ot += static_cast<uint64_t>(a.Tn)) {
+      double nx = 0.0, ny = 0.0;
+      if (noisy) draw_noise<kLaplace>(gm + ot, n, s_turn, s_log, &nx, &ny);
+      const double px = nom[0] + nx, py = nom[1] + ny;
+      const double dx = ex - px, dy = ey - py;
+      mo = min_f64(mo, fma(dx, dx, dy * dy));
+    }
+    if (valid) out[m] = min_f64(out[m], mo);
+    if (hits) count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(valid && mo < a.RR));
+  }
+  if (hits && count != 0 && (threadIdx.x & 63) == 0)
+    __hip_atomic_fetch_add(hits + b * (a.log_rows + 1) + static_cast<int64_t>(i),
+                           static_cast<unsigned long long>(count), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+}
+#endif
+
 }  // namespace
 
+#ifdef DRCVAR_LOOP_EVAL_LIBRARY
+extern "C" int drcvar_loop_clearance_f64_ex(
+    int64_t n_problems, const double* x0, int32_t n_states, const double* c_out,
+    const double* nominal_path, int64_t n_obstacles, int64_t path_steps, int64_t nom_so,
+    int64_t nom_st, const drcvar_step_state* state, int64_t step_begin, int64_t log_rows,
+    int64_t noise_steps, int32_t noise_kind, double p0, double p1, double p2, double combined_radius,
+    int64_t n_realizations, uint64_t seed, uint64_t eval_offset, uint64_t problem_offset_stride,
+    int32_t zero_first_step, double* min_d2, int64_t out_sb, int64_t* step_hits,
+    int32_t realizations_per_thread, void* stream) {
+  if (n_problems < 0 || n_obstacles < 0 || n_realizations < 0 || noise_steps < 0 ||
+      realizations_per_thread < 0 || (noise_kind != 0 && noise_kind != 1))
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (!(p0 == p0) || !(p1 == p1) || !(p2 == p2) || !(combined_radius >= 0.0))
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (noise_kind == 1 && (p0 < 0.0 || p1 < 0.0)) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (n_states < 1 || n_states > kMaxStates || path_steps < 1 || log_rows < 0)
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (n_problems == 0 || n_realizations == 0 || n_obstacles == 0) return DRCVAR_OK;  // no launch
+  if (!x0 || !c_out || !nominal_path || !state || !min_d2 ||
+      reinterpret_cast<uintptr_t>(state) % 16 != 0)
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  constexpr int64_t kMaxUnits = int64_t{1} << 20, kMaxReal = int64_t{1} << 40;
+  if (n_obstacles > kMaxUnits || noise_steps > kMaxUnits || n_obstacles * noise_steps > kMaxUnits ||
+      n_realizations > kMaxReal || realizations_per_thread > kMaxPerThread || n_problems > 65535)
+    return DRCVAR_ERR_UNSUPPORTED;
+  if (noise_steps == 0) return DRCVAR_OK;  // no step lies in [0, noise_steps): nothing is evaluated
+  const int64_t M = n_realizations, blocks = (M + kBlock - 1) / kBlock;
+  // Realisations per thread: one while the launch has fewer than kWantedLoopGroups workgroups
+  // (eight per CU: what is resident at once), then as many as keep that number, at most
+  // kRulePerThread; spread evenly over the chunks, so that the last one is not mostly empty.
+  // Measured: at B = 1024, M = 10000 the launch takes 149 us at 1 per thread,
+  // 128-129 us at 4 and 8, 142 us at 16 and 209 us at 32; at B <= 64 more than 2 only costs.
+  int64_t per = realizations_per_thread;
+  if (per == 0) {
+    per = std::min<int64_t>(std::max<int64_t>(n_problems * blocks / kWantedLoopGroups, 1), kRulePerThread);
+    const int64_t chunks = (blocks + per - 1) / per;
+    per = (blocks + chunks - 1) / chunks;
+  }
+  const int64_t gx = (blocks + per - 1) / per;
+  if (gx > 0x7fffffffLL) return DRCVAR_ERR_UNSUPPORTED;
+  LoopEvalArgs a{};
+  a.nom_so = nom_so;
+  a.nom_st = nom_st;
+  a.O = n_obstacles;
+  a.Tn = noise_steps;
+  a.OT = n_obstacles * noise_steps;
+  a.path_last = path_steps - 1;
+  a.step_begin = step_begin;
+  a.log_rows = log_rows;
+  a.M = M;
+  a.out_sb = out_sb;
+  a.eval_offset = eval_offset;
+  a.offset_stride = problem_offset_stride;
+  a.k0 = static_cast<uint32_t>(seed);
+  a.k1 = static_cast<uint32_t>(seed >> 32);
+  a.nx = n_states;
+  a.zero_first = zero_first_step != 0;
+  a.per_thread = static_cast<int>(per);
+  for (int j = 0; j < n_states; ++j) {  // copied at call time: c_out is host memory
+    a.cx[j] = c_out[j];
+    a.cy[j] = c_out[n_states + j];
+  }
+  a.p0 = p0;
+  a.p1 = p1;
+  a.p2 = p2;
+  a.RR = combined_radius * combined_radius;
+  a.lg = make_log_scale(noise_kind == 1 ? 0.5 : 1.0);
+  const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(n_problems));
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned long long* hits = reinterpret_cast<unsigned long long*>(step_hits);
+  (void)hipGetLastError();  // clear stale errors from unrelated work
+  if (noise_kind == 1)
+    hipLaunchKernelGGL(loop_clearance_kernel<true>, grid, dim3(kBlock), 0, s, x0, nominal_path, state,
+                       min_d2, hits, a);
+  else
+    hipLaunchKernelGGL(loop_clearance_kernel<false>, grid, dim3(kBlock), 0, s, x0, nominal_path, state,
+                       min_d2, hits, a);
+  return hipGetLastError() == hipSuccess ? DRCVAR_OK : DRCVAR_ERR_LAUNCH;
+}
+
+extern "C" int drcvar_loop_clearance_f64(
+    int64_t n_problems, const double* x0, int32_t n_states, const double* c_out,
+    const double* nominal_path, int64_t n_obstacles, int64_t path_steps, int64_t nom_so,
+    int64_t nom_st, const drcvar_step_state* state, int64_t step_begin, int64_t log_rows,
+    int64_t noise_steps, int32_t noise_kind, double p0, double p1, double p2, double combined_radius,
+    int64_t n_realizations, uint64_t seed, uint64_t eval_offset, uint64_t problem_offset_stride,
+    int32_t zero_first_step, double* min_d2, int64_t out_sb, int64_t* step_hits, void* stream) {
+  return drcvar_loop_clearance_f64_ex(n_problems, x0, n_states, c_out, nominal_path, n_obstacles,
+                                      path_steps, nom_so, nom_st, state, step_begin, log_rows,
+                                      noise_steps, noise_kind, p0, p1, p2, combined_radius,
+                                      n_realizations, seed, eval_offset, problem_offset_stride,
+                                      zero_first_step, min_d2, out_sb, step_hits, 0, stream);
+}
+#else
 extern "C" int drcvar_min_clearance_f64_ex(const double* ego, int64_t n_traj, int64_t ego_sk,
                                            int64_t ego_st, const double* nominal,
                                            int64_t n_obstacles, int64_t n_steps, int64_t nom_so,
@@ -281,3 +488,4 @@ extern "C" int drcvar_min_clearance_f64(const double* ego, int64_t n_traj, int64
                                      m_begin, n_realizations, seed, stream_offset,
                                      zero_first_step, min_clearance_out, out_sk, step_hits, 0, stream);
 }
+#endif

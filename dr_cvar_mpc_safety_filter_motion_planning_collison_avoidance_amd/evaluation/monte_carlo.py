@@ -96,6 +96,93 @@ def min_clearance_device(ego, nominal, n_realizations, *, noise="laplace", noise
     return (out, hits) if step_hits else out
 
 
+# ---- the loop form: the current state of B loops per launch (include/drcvar_loop_eval.h) ----------
+LOOP_EVAL_BLOCK = 256            # realisations one workgroup covers per realisation per thread
+LOOP_EVAL_RULE_PER_THREAD = 8    # the most realisations per thread the library's rule chooses
+LOOP_EVAL_MAX_PER_THREAD = 64    # ... and the most ``realizations_per_thread`` may ask for
+MAX_LOOP_STATES = 8
+
+
+def _loop_eval_check(x0, c_out, nominal_path, n_obstacles, state, min_d2, step_hits, log_rows):
+    """The buffers of a loop-evaluation launch against each other (host only: shapes, dtypes,
+    strides, devices).  Returns ``(B, nx, O, P, M, c_out as a contiguous host array)``."""
+    if not isinstance(x0, torch.Tensor) or x0.dtype != torch.float64 or x0.dim() != 2 or \
+            not x0.is_contiguous():
+        raise ValueError("x0 must be a contiguous float64 [B, nx] tensor")
+    B, nx = x0.shape
+    if B < 1 or not 1 <= nx <= MAX_LOOP_STATES:
+        raise ValueError(f"x0 is [B, nx] with B >= 1 and nx in 1..{MAX_LOOP_STATES}, got {tuple(x0.shape)}")
+    c = np.ascontiguousarray(np.asarray(c_out, dtype=np.float64))
+    if c.shape != (2, nx):
+        raise ValueError(f"c_out must be [2, {nx}] (the model's position rows), got {c.shape}")
+    O, rows = int(n_obstacles), int(log_rows)
+    if O < 1 or rows < 0:
+        raise ValueError("n_obstacles must be at least 1 and log_rows must not be negative")
+    t = nominal_path
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 3 or \
+            t.shape[0] != B * O or t.shape[1] < 1 or t.shape[2] != 2 or t.stride(2) != 1:
+        raise ValueError(f"nominal_path must be float64 [B O = {B * O}, P, 2] with adjacent coordinates")
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int64 or state.numel() != 2 * B or \
+            not state.is_contiguous() or state.shape[-1] != 2:
+        raise ValueError(f"state must be a contiguous int64 [B = {B}, 2] tensor ([stream_offset, step])")
+    if not isinstance(min_d2, torch.Tensor) or min_d2.dtype != torch.float64 or min_d2.dim() != 2 or \
+            min_d2.shape[0] != B or (min_d2.shape[1] > 1 and min_d2.stride(1) != 1):
+        raise ValueError(f"min_d2 must be a float64 [B = {B}, M] view with adjacent realisations")
+    if step_hits is not None and (not isinstance(step_hits, torch.Tensor) or
+                                  step_hits.dtype != torch.int64 or not step_hits.is_contiguous() or
+                                  tuple(step_hits.shape) != (B, rows + 1)):
+        raise ValueError(f"step_hits must be a contiguous int64 [B = {B}, log_rows + 1 = {rows + 1}] tensor")
+    for name, buf in (("nominal_path", t), ("state", state), ("min_d2", min_d2), ("step_hits", step_hits)):
+        if buf is not None and buf.device != x0.device:
+            raise ValueError(f"{name} must be on x0's device {x0.device}, got {buf.device}")
+    if x0.device.type != "cuda":
+        raise ValueError("the buffers must be device tensors (the evaluation kernel has no CPU path)")
+    return B, nx, O, t.shape[1], min_d2.shape[1], c
+
+
+def prepare_loop_clearance_step(x0, c_out, nominal_path, n_obstacles, state, min_d2, step_hits=None, *,
+                                step_begin=0, log_rows=0, noise_steps=None, noise="laplace",
+                                noise_cov=NOISE_COV, robot_radius, obstacle_radius, seed=0,
+                                eval_offset=0, problem_offset_stride=1, zero_first_step=True,
+                                realizations_per_thread=0, stream=None):
+    """Freeze one ``drcvar_loop_clearance_f64_ex`` call (``include/drcvar_loop_eval.h``) on
+    ``stream``: every call of the returned launch evaluates the state ``x0 [B, nx]`` each of B
+    loops is in NOW, at its path row ``state[b, 1]``, against ``M`` noise realisations of its
+    obstacles ``nominal_path [B O, P, 2]``, and accumulates ``min_d2 [B, M]`` (running minimum of
+    the squared distance; fill with +inf first) and ``step_hits [B, log_rows + 1]`` (collisions
+    per step since ``step_begin``; fill with 0 first; optional).  Capturable: nothing that changes
+    from step to step is frozen.  ``noise_steps`` (default P) is the T of the
+    ``min_clearance_device`` call whose draws these are: problem b at row s sees bit for bit that
+    call's noise at step s with ``stream_offset = eval_offset + b problem_offset_stride``."""
+    B, nx, O, P, M, c = _loop_eval_check(x0, c_out, nominal_path, n_obstacles, state, min_d2,
+                                         step_hits, log_rows)
+    kind, p0, p1, p2 = _noise_params(noise, noise_cov)
+    Tn = P if noise_steps is None else int(noise_steps)
+    per = int(realizations_per_thread)
+    if Tn < 0 or not 0 <= per <= LOOP_EVAL_MAX_PER_THREAD:
+        raise ValueError(f"noise_steps must not be negative and realizations_per_thread must be in "
+                         f"0..{LOOP_EVAL_MAX_PER_THREAD}")
+    from .. import engine
+    s = stream if stream is not None else torch.cuda.current_stream(x0.device)
+    vp, i32, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64
+    mask = 2 ** 64 - 1
+    return engine.PreparedLaunch(_native.eval_lib().drcvar_loop_clearance_f64_ex, (
+        B, vp(x0.data_ptr()), i32(nx), vp(c.ctypes.data), vp(nominal_path.data_ptr()), O, P,
+        nominal_path.stride(0), nominal_path.stride(1), vp(state.data_ptr()), int(step_begin),
+        int(log_rows), Tn, i32(kind), p0, p1, p2, float(robot_radius) + float(obstacle_radius), M,
+        u64(int(seed) & mask), u64(int(eval_offset) & mask), u64(int(problem_offset_stride) & mask),
+        i32(1 if zero_first_step else 0), vp(min_d2.data_ptr()), min_d2.stride(0),
+        vp(step_hits.data_ptr() if step_hits is not None else None), i32(per),
+        vp(int(s.cuda_stream))), (x0, c, nominal_path, state, min_d2, step_hits))
+
+
+def loop_clearance_step(x0, c_out, nominal_path, n_obstacles, state, min_d2, step_hits=None, **kw):
+    """One checked ``drcvar_loop_clearance_f64`` launch: :func:`prepare_loop_clearance_step`'s
+    arguments, issued once.  Returns ``(min_d2, step_hits)``, the accumulated buffers."""
+    prepare_loop_clearance_step(x0, c_out, nominal_path, n_obstacles, state, min_d2, step_hits, **kw)()
+    return min_d2, step_hits
+
+
 def laplace_realizations_host(nominal_trajectories, n_realizations, noise_cov=NOISE_COV):
     """``n_realizations`` lists of one Laplace realisation per obstacle, drawn as the reference
     draws them (main.py:61 via obstacles.py:79-113): obstacles in order, on the global

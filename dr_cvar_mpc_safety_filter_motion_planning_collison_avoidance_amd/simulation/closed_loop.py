@@ -22,17 +22,26 @@ reference does (``main.py:95-97``), not about the actual state.  One problem per
 :class:`RecedingHorizonBatch` advances B loops in lockstep with the same three launches per step
 (``drcvar_mpc_step_advance_batch_f64``, ``include/drcvar_loop.h``: one workgroup and one device state per problem, DESIGN.md
 §5.4).
+
+Both classes take ``evaluate=LoopEvaluation(...)``: a fourth launch per control step
+(``drcvar_loop_clearance_f64``, ``include/drcvar_loop_eval.h``) then holds the state just reached
+against M noise realisations of the obstacles and keeps the running minimum clearance and the
+per-step collision counts on the device; ``safety()`` returns them.  With
+``evaluate=None`` a step is the three launches above and nothing else changes.
 """
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 
 import torch
 
 from .. import _native, engine
+from ..evaluation import metrics, monte_carlo
 from ..core.mpc_filter import (DEFAULT_MAX_ITER, DEFAULT_TOL, METRIC_COLUMNS, MPCModel, filter_batch,
                                record_views)
 from ..engine import DEFAULT_NOISE_COV
+from .obstacles import NOISE_COV
 
 BACKENDS = ("graph", "launches", "reference")
 _MASK64 = 2 ** 64 - 1
@@ -76,7 +85,188 @@ def _capture_chain(dev, make_step, mutable, steps_per_graph):
     return graph
 
 
-class RecedingHorizonFilter:
+@dataclasses.dataclass(frozen=True)
+class LoopEvaluation:
+    """Out-of-sample collision evaluation of a loop while it runs (``evaluate=`` of the two loop
+    classes): every control step also updates, on the device, the running minimum
+    clearance of each loop against ``n_realizations`` noise realisations of its obstacles and the
+    per-step collision counts (``drcvar_loop_clearance_f64``, ``include/drcvar_loop_eval.h``).
+
+    The realisations are those of ``evaluation.monte_carlo.min_clearance_device`` for (``noise``,
+    ``noise_cov``, ``seed``, ``stream_offset`` [+ b with ``independent_problems``], O obstacles,
+    ``T = noise_steps`` steps, default the paths' P rows, noise-free path row 0): a loop at path
+    row s meets realisation m's obstacles of step s.  ``independent_problems=False`` gives every
+    problem of a batch the same realisations (common random numbers across loops)."""
+
+    n_realizations: int
+    noise: str = "laplace"
+    noise_cov: object = NOISE_COV
+    robot_radius: float = None
+    obstacle_radius: float = None
+    seed: int = 0
+    stream_offset: int = 0
+    independent_problems: bool = True
+    noise_steps: int = None
+
+    def validate(self):
+        """Host-only argument checks; returns ``self``."""
+        if isinstance(self.n_realizations, bool) or int(self.n_realizations) != self.n_realizations \
+                or not 1 <= int(self.n_realizations) <= 2 ** 40:
+            raise ValueError(f"n_realizations={self.n_realizations!r} must be an integer in 1..2^40")
+        monte_carlo._noise_params(self.noise, self.noise_cov)       # raises on an unknown kind
+        for name in ("robot_radius", "obstacle_radius"):
+            v = getattr(self, name)
+            if v is None or not float(v) >= 0.0:
+                raise ValueError(f"{name}={v!r} must be given and must not be negative")
+        if self.noise_steps is not None and int(self.noise_steps) < 1:
+            raise ValueError(f"noise_steps={self.noise_steps} must be at least 1 (or None: the paths' rows)")
+        return self
+
+    @property
+    def combined_radius(self):
+        return float(self.robot_radius) + float(self.obstacle_radius)
+
+
+def check_evaluated_steps(first, last, noise_steps):
+    """An evaluated loop may only visit path rows ``0 <= s < noise_steps`` (host only): a loop
+    never silently stops being evaluated."""
+    if first < 0 or last >= noise_steps:
+        raise ValueError(f"an evaluated loop visits path rows {first}..{last}, outside the "
+                         f"evaluation's 0..{noise_steps - 1} (LoopEvaluation.noise_steps)")
+
+
+def check_evaluate(evaluate):
+    """The ``evaluate=`` argument of the loop classes (host only)."""
+    if evaluate is not None:
+        if not isinstance(evaluate, LoopEvaluation):
+            raise ValueError("evaluate must be a LoopEvaluation or None")
+        evaluate.validate()
+
+
+class _Evaluated:
+    """What the two loop classes share for ``evaluate=``: the buffers, the launch appended to a
+    control step, and :meth:`safety`.  The single class is the batch of one problem here
+    (``_eval_B = 1``; its ``[...]`` buffers are viewed with a leading problem dimension)."""
+
+    evaluate = None
+
+    def _eval_init(self, evaluate, n_problems, n_obstacles, nominal_flat):
+        self.evaluate = evaluate
+        self._eval_B, self._eval_O, self._eval_nominal = n_problems, n_obstacles, nominal_flat
+        self._eval_hits = None
+        if evaluate is None:
+            return
+        self._noise_steps = int(evaluate.noise_steps) if evaluate.noise_steps is not None \
+            else self.path_steps
+        self._eval_C = torch.as_tensor(self.model.C, dtype=torch.float64).reshape(2, self.model.nx)
+        self._min_d2 = torch.full((n_problems, int(evaluate.n_realizations)), float("inf"),
+                                  dtype=torch.float64, device=self.model.device)
+        self._eval_history, self._eval_mode, self._eval_first = [], None, 0
+
+    def _eval_batched(self, t):
+        """A per-problem buffer with its leading problem dimension."""
+        return t if isinstance(self, RecedingHorizonBatch) else t.unsqueeze(0)
+
+    def _eval_launch(self, stream):
+        ev = self.evaluate
+        return monte_carlo.prepare_loop_clearance_step(
+            self._x0, self._eval_C.numpy(), self._eval_nominal, self._eval_O,
+            self._state.view(self._eval_B, 2), self._min_d2, self._eval_hits,
+            step_begin=self._step_begin, log_rows=self._cap, noise_steps=self._noise_steps,
+            noise=ev.noise, noise_cov=ev.noise_cov, robot_radius=ev.robot_radius,
+            obstacle_radius=ev.obstacle_radius, seed=ev.seed, eval_offset=ev.stream_offset,
+            problem_offset_stride=1 if ev.independent_problems else 0, zero_first_step=True,
+            stream=stream)
+
+    def _eval_rebase(self, cap, carry):
+        """New per-step counts with the new logs; with ``carry`` (a rebase inside a run) row 0
+        takes over the old table's count of the current state, as ``x_log``'s row 0 is the current
+        state, and the rows before it are remembered for the ``reference`` backend."""
+        if self.evaluate is None:
+            return
+        old, i = self._eval_hits, getattr(self, "_i", 0)
+        self._eval_hits = torch.zeros((self._eval_B, cap + 1), dtype=torch.int64,
+                                      device=self.model.device)
+        if carry and old is not None:
+            self._eval_hits[:, 0].copy_(old[:, i])
+            self._eval_history.append(self._eval_batched(self._logs[0])[:, :i].clone())
+
+    def _eval_reset(self):
+        """After ``reset`` has settled the logs: +inf, zero counts, and the initial state (log row
+        0) evaluated by one eager launch."""
+        if self.evaluate is None:
+            return
+        self._min_d2.fill_(float("inf"))
+        self._eval_hits.zero_()
+        self._eval_history, self._eval_mode, self._eval_first = [], None, self._step
+        self._eval_launch(torch.cuda.current_stream(self.model.device))()
+
+    def _eval_check_run(self, n, backend):
+        if self.evaluate is None:
+            return
+        check_evaluated_steps(self._step, self._step + int(n), self._noise_steps)
+        mode = "reference" if backend == "reference" else "device"
+        if int(n) > 0:
+            if getattr(self, "_eval_mode", None) not in (None, mode):
+                raise ValueError("an evaluated loop cannot mix the reference backend with the "
+                                 "device backends between two resets")
+            self._eval_mode = mode
+
+    def _reference_safety(self):
+        """(min_clearance [B, M], step_hits [B, rows]) after the fact, from entries that predate
+        the loop form: per problem one ``min_clearance_device`` call (K = 1, T = noise_steps) on an
+        ego whose visited rows hold the logged positions and whose other rows lie 1e3 away from
+        every obstacle's nominal row."""
+        ev, dev = self.evaluate, self.model.device
+        Tn, O, M = self._noise_steps, self._eval_O, int(ev.n_realizations)
+        x_log = self._eval_batched(self._logs[0])
+        states = torch.cat(self._eval_history + [x_log[:, :self._i + 1]], dim=1)
+        pos = states @ self._eval_C.to(dev).T                                   # [B, visited, 2]
+        first = self._eval_first
+        rows = torch.arange(Tn, device=dev).clamp_(max=self.path_steps - 1)
+        clearance, hits = [], []
+        for b in range(self._eval_B):
+            nominal = self._eval_nominal[b * O:(b + 1) * O].index_select(1, rows)   # [O, Tn, 2]
+            ego = torch.stack((nominal[..., 0].max(dim=0).values + 1e3, nominal[0, :, 1]), dim=1)
+            ego[first:first + pos.shape[1]] = pos[b]
+            offset = ev.stream_offset + (b if ev.independent_problems else 0)
+            c, h = monte_carlo.min_clearance_device(
+                ego[None], nominal, M, noise=ev.noise, noise_cov=ev.noise_cov,
+                robot_radius=ev.robot_radius, obstacle_radius=ev.obstacle_radius, seed=ev.seed,
+                stream_offset=offset, zero_first_step=True, step_hits=True)
+            clearance.append(c[0])
+            hits.append(h[0, self._step_begin:self._step_begin + self._i + 1])
+        return torch.stack(clearance), torch.stack(hits)
+
+    def safety(self):
+        """The safety statistics since ``reset``, device tensors (the single class drops the
+        leading problem dimension): ``min_clearance [B, M]`` = sqrt(min d^2) - R, ``collided [B]``
+        the fraction of realisations in collision at some visited state, ``step_hits [B, rows]``
+        and ``step_collision_rate`` for the states since the last rebase (row 0: the state the
+        logs start from), and ``metrics``, ``evaluation.metrics.safety_metrics`` per problem."""
+        if self.evaluate is None:
+            raise RuntimeError("the loop was built without evaluate=")
+        if not self._primed:
+            raise RuntimeError("call reset(x0) before safety()")
+        R = self.evaluate.combined_radius
+        f64 = dict(dtype=torch.float64, device=self.model.device)
+        if self._eval_mode == "reference":
+            clearance, hits = self._reference_safety()
+            collided = clearance < 0
+        else:
+            clearance = torch.sqrt(self._min_d2) - R
+            hits = self._eval_hits[:, :self._i + 1].clone()
+            collided = self._min_d2 < R * R
+        M = torch.full((), float(clearance.shape[1]), **f64)   # a tensor divisor (monte_carlo.py)
+        result = {"min_clearance": clearance, "collided": collided.sum(dim=1).to(torch.float64) / M,
+                  "step_hits": hits, "step_collision_rate": hits.to(torch.float64) / M,
+                  "metrics": [metrics.safety_metrics(row) for row in clearance]}
+        if not isinstance(self, RecedingHorizonBatch):
+            result = {k: v[0] for k, v in result.items()}
+        return result
+
+
+class RecedingHorizonFilter(_Evaluated):
     """One problem's receding-horizon loop.
 
     ``nominal_path [O, P, 2]`` (obstacles), ``x_ref_path [P, nx]`` and ``u_ref_path [P, nu]`` are
@@ -98,11 +288,12 @@ class RecedingHorizonFilter:
     def __init__(self, model: MPCModel, nominal_path, x_ref_path, u_ref_path, n_samples, params, *,
                  metric="dr_cvar", noise_cov=DEFAULT_NOISE_COV, chol=None, seed=0,
                  zero_first_step=True, max_iter=DEFAULT_MAX_ITER, tol=DEFAULT_TOL, polish=True,
-                 options=None, disturbance=None, steps_per_graph=1):
+                 options=None, disturbance=None, steps_per_graph=1, evaluate=None):
         if metric not in METRIC_COLUMNS:
             raise ValueError(f"metric must be one of {tuple(METRIC_COLUMNS)}, got {metric!r}")
         if int(steps_per_graph) < 1:
             raise ValueError(f"steps_per_graph={steps_per_graph} must be at least 1")
+        check_evaluate(evaluate)
         n = int(n_samples)
         if n < 1 or n > _native.MAX_SAMPLES:
             raise ValueError(f"n_samples={n} outside 1..{_native.MAX_SAMPLES}")
@@ -148,6 +339,7 @@ class RecedingHorizonFilter:
         self._info = torch.zeros((1, _native.MPC_INFO_WIDTH), **f64)
         self._workspace = torch.empty(max(model.workspace_doubles(1, O), 1), **f64)
         self._rows = {k: torch.arange(k, device=dev) for k in (H, H + 1)}
+        self._eval_init(evaluate, 1, O, nominal_path)
         self._logs = None           # (x_log [cap + 1, nx], u_log [cap, nu], info_log [cap, 10])
         self._cap, self._step_begin = 0, 0
         self._primed = False
@@ -166,6 +358,8 @@ class RecedingHorizonFilter:
         reference inputs: no optimum is remembered yet)."""
         dev = self.model.device
         H = self.model.horizon
+        if self.evaluate is not None:
+            check_evaluated_steps(int(step), int(step), self._noise_steps)
         x0 = torch.as_tensor(x0, dtype=torch.float64).reshape(1, self.model.nx).to(dev)
         self._step, self._offset = int(step), int(stream_offset) & _MASK64
         self._state.copy_(torch.tensor([_signed64(self._offset), self._step], dtype=torch.int64))
@@ -184,10 +378,12 @@ class RecedingHorizonFilter:
             self._i = 0
         else:
             self._rebase(cap)
+        self._eval_reset()
 
-    def _rebase(self, cap):
+    def _rebase(self, cap, carry=False):
         """New logs of ``cap`` rows whose row 0 is the current step (captured launches freeze the
         log pointers and the first step, so they are dropped)."""
+        self._eval_rebase(cap, carry)
         nx, nu = self.model.nx, self.model.nu
         f64 = dict(dtype=torch.float64, device=self.model.device)
         nan = float("nan")
@@ -220,6 +416,9 @@ class RecedingHorizonFilter:
             vp(self._last_u.data_ptr()), vp(self._have_last.data_ptr()), vp(self._state.data_ptr()),
             vp(int(stream.cuda_stream))), (self, x_log, u_log, info_log))
         out = (self._x, self._u, self._info)
+        # with an evaluation: a fourth launch on the same stream, after the advance (x0 is then the
+        # state just reached and state.step its path row); the chain stays linear
+        evaluation = self._eval_launch(stream) if self.evaluate is not None else None
 
         def step():
             halfspaces()
@@ -227,11 +426,14 @@ class RecedingHorizonFilter:
                          self.tol, self.polish, workspace=self._workspace, stream=stream,
                          options=self.options, out=out)
             advance()
+            if evaluation is not None:
+                evaluation()
         return step
 
     def _mutable(self):
+        evaluated = [] if self.evaluate is None else [self._min_d2, self._eval_hits]
         return [self._state, self._x0, self._x_ref_win, self._u_fb, self._last_u, self._have_last,
-                *self._logs]
+                *self._logs, *evaluated]
 
     def _capture(self):
         return _capture_chain(self.model.device, self._make_step, self._mutable, self.steps_per_graph)
@@ -277,11 +479,12 @@ class RecedingHorizonFilter:
         if not self._primed:
             raise RuntimeError("call reset(x0) before run()")
         n = int(n_steps)
+        self._eval_check_run(n, backend)
         if self._i + n > self._cap:
             if self.disturbance is not None:
                 raise ValueError(f"{self._i + n} steps since reset, but disturbance has "
                                  f"{self.disturbance.shape[0]} rows")
-            self._rebase(max(n, _MIN_LOG_ROWS))
+            self._rebase(max(n, _MIN_LOG_ROWS), carry=True)
         i0 = self._i
         dev = self.model.device
         if n == 0:
@@ -348,7 +551,7 @@ def batch_x0(x0, n_problems: int, nx: int) -> torch.Tensor:
     return x0
 
 
-class RecedingHorizonBatch:
+class RecedingHorizonBatch(_Evaluated):
     """``n_problems`` receding-horizon loops that advance in lockstep: three launches per control
     step for any B.
 
@@ -382,11 +585,12 @@ class RecedingHorizonBatch:
     def __init__(self, model: MPCModel, nominal_path, x_ref_path, u_ref_path, n_samples, params, *,
                  n_problems, metric="dr_cvar", noise_cov=DEFAULT_NOISE_COV, chol=None, seed=0,
                  zero_first_step=True, max_iter=DEFAULT_MAX_ITER, tol=DEFAULT_TOL, polish=True,
-                 options=None, disturbance=None, steps_per_graph=1):
+                 options=None, disturbance=None, steps_per_graph=1, evaluate=None):
         if metric not in METRIC_COLUMNS:
             raise ValueError(f"metric must be one of {tuple(METRIC_COLUMNS)}, got {metric!r}")
         if int(steps_per_graph) < 1:
             raise ValueError(f"steps_per_graph={steps_per_graph} must be at least 1")
+        check_evaluate(evaluate)
         n = int(n_samples)
         if n < 1 or n > _native.MAX_SAMPLES:
             raise ValueError(f"n_samples={n} outside 1..{_native.MAX_SAMPLES}")
@@ -428,6 +632,7 @@ class RecedingHorizonBatch:
         self._info = torch.zeros((B, _native.MPC_INFO_WIDTH), **f64)
         self._workspace = torch.empty(max(model.workspace_doubles(B, O), 1), **f64)
         self._rows = {k: torch.arange(k, device=dev) for k in (H, H + 1)}
+        self._eval_init(evaluate, B, O, self.nominal_path)
         self._logs = None           # (x_log [B, cap + 1, nx], u_log [B, cap, nu], info_log [B, cap, 10])
         self._cap, self._step_begin = 0, 0
         self._primed = False
@@ -455,6 +660,8 @@ class RecedingHorizonBatch:
         for all) with the stream offset of their first draw; all B device states are filled
         identically."""
         H = self.model.horizon
+        if self.evaluate is not None:
+            check_evaluated_steps(int(step), int(step), self._noise_steps)
         x0 = batch_x0(x0, self.n_problems, self.model.nx).to(self.model.device)
         self._step, self._offset = int(step), int(stream_offset) & _MASK64
         self._write_state()
@@ -473,10 +680,12 @@ class RecedingHorizonBatch:
             self._i = 0
         else:
             self._rebase(cap)
+        self._eval_reset()
 
-    def _rebase(self, cap):
+    def _rebase(self, cap, carry=False):
         """New logs of ``cap`` rows per problem whose row 0 is the current step (captured launches
         freeze the log pointers, the row count and the first step, so they are dropped)."""
+        self._eval_rebase(cap, carry)
         B, nx, nu = self.n_problems, self.model.nx, self.model.nu
         f64 = dict(dtype=torch.float64, device=self.model.device)
         nan = float("nan")
@@ -508,6 +717,9 @@ class RecedingHorizonBatch:
             vp(self._last_u.data_ptr()), vp(self._have_last.data_ptr()), vp(self._state.data_ptr()),
             vp(int(stream.cuda_stream))), (self, x_log, u_log, info_log))
         out = (self._x, self._u, self._info)
+        # with an evaluation: a fourth launch on the same stream, after the advance (x0 is then the
+        # state just reached and state.step its path row); the chain stays linear
+        evaluation = self._eval_launch(stream) if self.evaluate is not None else None
 
         def step():
             halfspaces()
@@ -515,11 +727,14 @@ class RecedingHorizonBatch:
                          self.tol, self.polish, workspace=self._workspace, stream=stream,
                          options=self.options, out=out)
             advance()
+            if evaluation is not None:
+                evaluation()
         return step
 
     def _mutable(self):
+        evaluated = [] if self.evaluate is None else [self._min_d2, self._eval_hits]
         return [self._state, self._x0, self._x_ref_win, self._u_fb, self._last_u, self._have_last,
-                *self._logs]
+                *self._logs, *evaluated]
 
     # ---- the semantics, from the entry points that predate the loop -----------------------------
     def _reference_step(self, i):
@@ -562,11 +777,12 @@ class RecedingHorizonBatch:
         if not self._primed:
             raise RuntimeError("call reset(x0) before run()")
         n = int(n_steps)
+        self._eval_check_run(n, backend)
         if self._i + n > self._cap:
             if self.disturbance is not None:
                 raise ValueError(f"{self._i + n} steps since reset, but disturbance has "
                                  f"{self.disturbance.shape[1]} rows")
-            self._rebase(max(n, _MIN_LOG_ROWS))
+            self._rebase(max(n, _MIN_LOG_ROWS), carry=True)
         i0 = self._i
         dev = self.model.device
         if n == 0:

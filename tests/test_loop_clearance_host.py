@@ -1,0 +1,148 @@
+"""CPU: the host side of drcvar_loop_clearance_f64[_ex] (include/drcvar_loop_eval.h) and of the
+evaluate= surface of the loop classes.  Every call here returns or raises before any launch: no
+pointer is device memory and no device is reached."""
+import ctypes
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd import _native
+from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd.core.mpc_filter import MPCModel
+from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd.engine import RiskParams
+from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd.simulation import closed_loop
+from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd.simulation.closed_loop import LoopEvaluation
+
+INV, UNS, OK = _native.ERR_INVALID_ARGUMENT, _native.ERR_UNSUPPORTED, _native.OK
+POINTERS = ("x0", "c_out", "nominal_path", "state", "min_d2")
+C_OUT = (ctypes.c_double * 16)(*([0.0] * 16))
+
+
+def _call(lib, ex=None, **kw):
+    """The entry with host values that pass every check unless ``kw`` says otherwise (the device
+    pointers are the address 64: a launch would follow, so every case here must return first)."""
+    a = dict(B=3, x0=64, nx=4, c_out=ctypes.addressof(C_OUT), nominal_path=64, O=2, P=9, nom_so=18,
+             nom_st=2, state=64, step_begin=0, log_rows=5, Tn=9, kind=1, p0=0.1, p1=0.1, p2=0.0, R=0.5,
+             M=100, seed=1, offset=0, stride=1, zero_first=1, min_d2=64, out_sb=100, step_hits=64)
+    a.update(kw)
+    vp = ctypes.c_void_p
+    args = [a["B"], vp(a["x0"]), a["nx"], vp(a["c_out"]), vp(a["nominal_path"]), a["O"], a["P"],
+            a["nom_so"], a["nom_st"], vp(a["state"]), a["step_begin"], a["log_rows"], a["Tn"],
+            a["kind"], a["p0"], a["p1"], a["p2"], a["R"], a["M"], a["seed"], a["offset"], a["stride"],
+            a["zero_first"], vp(a["min_d2"]), a["out_sb"], vp(a["step_hits"])]
+    if ex is None:
+        return lib.drcvar_loop_clearance_f64(*args, None)
+    return lib.drcvar_loop_clearance_f64_ex(*args, ex, None)
+
+
+def test_eval_library_exports_what_its_header_declares():
+    text = re.sub(r"/\*.*?\*/", "", open(_native.EVAL_HEADER).read(), flags=re.S)
+    declared = sorted(set(re.findall(r"^\s*(?:const\s+)?\w+\s*\*?\s*(drcvar_\w+)\s*\(", text, flags=re.M)))
+    assert declared == sorted(_native.EVAL_SYMBOLS)
+    assert declared == ["drcvar_loop_clearance_f64", "drcvar_loop_clearance_f64_ex"]
+    assert not set(declared) & (set(_native.EXPORTED_SYMBOLS) | set(_native.LOOP_SYMBOLS))
+    lib = _native.eval_lib()
+    out = subprocess.run(["nm", "-D", "--defined-only", _native.EVAL_LIB_PATH], capture_output=True,
+                         text=True, check=True).stdout
+    assert set(re.findall(r"\bT (drcvar_\w+)", out)) == set(declared)
+    assert b"gfx950" in open(_native.EVAL_LIB_PATH, "rb").read()
+    plain, ex = lib.drcvar_loop_clearance_f64.argtypes, lib.drcvar_loop_clearance_f64_ex.argtypes
+    assert ex == plain[:-1] + [ctypes.c_int32, ctypes.c_void_p]
+    # the other two libraries export what they did
+    for path, symbols in ((_native.LIB_PATH, _native.EXPORTED_SYMBOLS),
+                          (_native.LOOP_LIB_PATH, _native.LOOP_SYMBOLS)):
+        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True,
+                             check=True).stdout
+        assert set(re.findall(r"\bT (drcvar_\w+)", out)) == set(symbols), path
+    assert len(_native.EXPORTED_SYMBOLS) == 33 and len(_native.LOOP_SYMBOLS) == 1
+
+
+@pytest.mark.parametrize("ex", [None, 0, 4])
+def test_host_validation(ex):
+    lib = _native.eval_lib()
+    nan = float("nan")
+    invalid = [dict(B=-1), dict(O=-1), dict(M=-1), dict(Tn=-1), dict(p0=nan), dict(p1=nan),
+               dict(p2=nan), dict(R=nan), dict(R=-0.5), dict(kind=2), dict(kind=-1), dict(nx=0),
+               dict(nx=9), dict(P=0), dict(P=-3), dict(log_rows=-1), dict(p0=-0.1), dict(p1=-0.1)]
+    for kw in invalid:
+        assert _call(lib, ex, **kw) == INV, kw
+        assert _call(lib, ex, B=0, **{k: v for k, v in kw.items() if k != "B"}) in (INV, OK)
+    assert _call(lib, ex, kind=0, p0=-0.1, M=0) == OK       # (a Cholesky entry may be negative)
+    for null in POINTERS:
+        assert _call(lib, ex, **{null: None}) == INV, null
+    for off in (1, 4, 8, 12):
+        assert _call(lib, ex, state=64 + off) == INV, off
+    # nothing to launch: no pointer is looked at
+    nulls = {name: None for name in POINTERS}
+    for empty in (dict(B=0), dict(M=0), dict(O=0)):
+        assert _call(lib, ex, **empty) == OK and _call(lib, ex, step_hits=None, **empty, **nulls) == OK
+    assert _call(lib, ex, Tn=0) == OK
+    # the limits
+    for kw in (dict(O=2 ** 10 + 1, Tn=2 ** 10), dict(O=2 ** 20 + 1, Tn=1), dict(O=1, Tn=2 ** 20 + 1),
+               dict(O=2 ** 40, Tn=2 ** 40), dict(M=2 ** 40 + 1), dict(B=65536), dict(B=2 ** 31)):
+        assert _call(lib, ex, **kw) == UNS, kw
+        assert _call(lib, ex, state=None, **kw) == INV         # an invalid call stays invalid
+    lib_ex = lambda per, **kw: _call(lib, per, **kw)
+    assert lib_ex(-1) == INV and lib_ex(65) == UNS and lib_ex(65, B=0) == OK
+
+
+def _model(horizon=4):
+    dt = 0.2
+    A = np.array([[1, 0, dt, 0], [0, 1, 0, dt], [0, 0, 1, 0], [0, 0, 0, 1]], dtype=np.float64)
+    B = np.array([[0.5 * dt * dt, 0], [0, 0.5 * dt * dt], [dt, 0], [0, dt]], dtype=np.float64)
+    C = np.array([[1, 0, 0, 0], [0, 1, 0, 0]], dtype=np.float64)
+    return MPCModel(A, B, C, np.eye(4), 0.1 * np.eye(2), horizon, device="cpu")
+
+
+def test_loop_evaluation_settings():
+    ok = LoopEvaluation(100, robot_radius=0.3, obstacle_radius=0.2)
+    assert ok.validate() is ok and ok.combined_radius == 0.5
+    assert (ok.noise, ok.seed, ok.stream_offset, ok.independent_problems, ok.noise_steps) == \
+        ("laplace", 0, 0, True, None)
+    bad = [dict(n_realizations=0), dict(n_realizations=-3), dict(n_realizations=2.5),
+           dict(n_realizations=2 ** 40 + 1), dict(noise="cauchy"), dict(robot_radius=None),
+           dict(obstacle_radius=None), dict(robot_radius=-0.1), dict(obstacle_radius=float("nan")),
+           dict(noise_steps=0), dict(noise_steps=-2)]
+    for kw in bad:
+        a = dict(n_realizations=100, robot_radius=0.3, obstacle_radius=0.2)
+        a.update(kw)
+        with pytest.raises(ValueError):
+            LoopEvaluation(**a).validate()
+
+
+def test_constructors_reject_a_bad_evaluation_before_the_device():
+    m = _model()
+    f64 = torch.float64
+    nominal, x_ref, u_ref = torch.zeros((3, 2, 9, 2), dtype=f64), torch.zeros((9, 4), dtype=f64), \
+        torch.zeros((9, 2), dtype=f64)
+    for evaluate in ("laplace", 100, LoopEvaluation(0, robot_radius=0.3, obstacle_radius=0.2),
+                     LoopEvaluation(10, robot_radius=0.3)):
+        with pytest.raises(ValueError, match="evaluate|n_realizations|obstacle_radius"):
+            closed_loop.RecedingHorizonBatch(m, nominal, x_ref, u_ref, 100, RiskParams(), n_problems=3,
+                                             evaluate=evaluate)
+        with pytest.raises(ValueError, match="evaluate|n_realizations|obstacle_radius"):
+            closed_loop.RecedingHorizonFilter(m, nominal[0], x_ref, u_ref, 100, RiskParams(),
+                                              evaluate=evaluate)
+
+
+@pytest.mark.parametrize("cls", [closed_loop.RecedingHorizonFilter, closed_loop.RecedingHorizonBatch])
+def test_run_past_noise_steps_raises_before_any_launch(cls):
+    """run() would reach path row _step + n; at or past noise_steps it raises, before the loop's
+    buffers are looked at (this object has none)."""
+    loop = cls.__new__(cls)
+    loop.steps_per_graph, loop._primed = 1, True
+    loop.evaluate = LoopEvaluation(10, robot_radius=0.3, obstacle_radius=0.2, noise_steps=12)
+    loop._noise_steps, loop._step = 12, 4
+    for n, backend in ((8, "graph"), (8, "launches"), (8, "reference"), (100, "graph")):
+        with pytest.raises(ValueError, match="noise_steps"):
+            loop.run(n, backend=backend)
+    with pytest.raises(AttributeError):      # 7 steps reach row 11: allowed, the loop goes on
+        loop.run(7, backend="launches")
+    closed_loop.check_evaluated_steps(0, 11, 12)
+    for first, last in ((-1, 3), (0, 12), (12, 12)):
+        with pytest.raises(ValueError):
+            closed_loop.check_evaluated_steps(first, last, 12)
+    with pytest.raises(RuntimeError):
+        cls.__new__(cls).safety()
