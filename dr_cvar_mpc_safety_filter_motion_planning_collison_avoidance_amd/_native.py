@@ -1,7 +1,8 @@
 """Loader for the HIP engine (``_lib/libdrcvar_halfspace.so``) — the C ABI of
 ``include/drcvar_halfspace.h`` (+ ``drcvar_mpc.h``, ``drcvar_sampling.h``, ``drcvar_exchange.h``)
-bound with ctypes; beside it the loop library (``drcvar_loop.h``, :func:`loop_lib`) and the
-loop-evaluation library (``drcvar_loop_eval.h``, :func:`eval_lib`), one entry family each.
+bound with ctypes; beside it the loop library (``drcvar_loop.h``, :func:`loop_lib`), the
+loop-evaluation library (``drcvar_loop_eval.h``, :func:`eval_lib`) and the predicted-ego library
+(``drcvar_loop_pred.h``, :func:`pred_lib`), one entry family each.
 
 There is deliberately no fallback: if the shared library is missing or cannot be loaded every
 entry point raises :class:`NativeLibraryError`.  ``build()`` compiles it for gfx950 in-tree.
@@ -40,6 +41,13 @@ EVAL_LIB_PATH = os.path.join(LIB_DIR, "libdrcvar_loop_eval.so")
 EVAL_HEADER = os.path.join(INCLUDE_DIR, "drcvar_loop_eval.h")
 EVAL_UNIT = (os.path.join(PKG_DIR, "csrc", "drcvar_clearance.hip"), ("-DDRCVAR_LOOP_EVAL_LIBRARY",))
 EVAL_SYMBOLS = ("drcvar_loop_clearance_f64", "drcvar_loop_clearance_f64_ex")
+# The predicted-ego library (include/drcvar_loop_pred.h), by the same recipe:
+# csrc/drcvar_sampled.hip compiled once more, with DRCVAR_LOOP_PRED_LIBRARY (14 kernels: the seven
+# plans x ISO of the predicted-ego form, none of the engine library's 28).
+PRED_LIB_PATH = os.path.join(LIB_DIR, "libdrcvar_loop_pred.so")
+PRED_HEADER = os.path.join(INCLUDE_DIR, "drcvar_loop_pred.h")
+PRED_UNIT = (os.path.join(PKG_DIR, "csrc", "drcvar_sampled.hip"), ("-DDRCVAR_LOOP_PRED_LIBRARY",))
+PRED_SYMBOLS = ("drcvar_sampled_halfspaces_f64_pred",)
 
 ABI_VERSION = 3
 OUT_WIDTH = 8
@@ -266,11 +274,11 @@ def build(verbose: bool = False, extra_flags=()) -> str:
     os.makedirs(obj_dir, exist_ok=True)
     import glob
     incs = sorted(glob.glob(os.path.join(PKG_DIR, "csrc", "*.inc")))  # tables the sources include
-    headers = b"".join(open(h, "rb").read() for h in HEADERS + [LOOP_HEADER, EVAL_HEADER] + incs)
+    headers = b"".join(open(h, "rb").read() for h in HEADERS + [LOOP_HEADER, EVAL_HEADER, PRED_HEADER] + incs)
     # the compiler's identity is part of every key: objects of an older hipcc / ROCm are rebuilt
     toolchain = _toolchain(probe=True)
     objs, procs = [], []
-    for src, defs in _compile_units() + [LOOP_UNIT, EVAL_UNIT]:
+    for src, defs in _compile_units() + [LOOP_UNIT, EVAL_UNIT, PRED_UNIT]:
         flags = _unit_flags(defs, extra_flags)
         key = hashlib.sha256(open(src, "rb").read() + headers + toolchain
                              + " ".join(flags).encode()).hexdigest()[:16]
@@ -288,9 +296,9 @@ def build(verbose: bool = False, extra_flags=()) -> str:
         raise subprocess.CalledProcessError(1, failed[0])
     for _, obj, _ in procs:
         os.replace(obj + ".tmp", obj)
-    # (LOOP_UNIT and EVAL_UNIT are the last two: each is a library of its own)
-    for path, members in ((LIB_PATH, objs[:-2]), (LOOP_LIB_PATH, objs[-2:-1]),
-                          (EVAL_LIB_PATH, objs[-1:])):
+    # (LOOP_UNIT, EVAL_UNIT and PRED_UNIT are the last three: each is a library of its own)
+    for path, members in ((LIB_PATH, objs[:-3]), (LOOP_LIB_PATH, objs[-3:-2]),
+                          (EVAL_LIB_PATH, objs[-2:-1]), (PRED_LIB_PATH, objs[-1:])):
         link = ["hipcc", f"--offload-arch={OFFLOAD_ARCH}", "-shared", "-fPIC", *members,
                 "-o", path + ".tmp"]
         if verbose:
@@ -480,6 +488,36 @@ def eval_lib():
             handle.drcvar_loop_clearance_f64_ex.restype = ctypes.c_int
             _eval_lib = handle
     return _eval_lib
+
+
+_pred_lib = None
+
+
+def pred_lib():
+    """The loaded predicted-ego library (``include/drcvar_loop_pred.h``; raises NativeLibraryError
+    if it is not built: there is no fallback).  It shares the engine library's structs and return
+    codes."""
+    global _pred_lib
+    if _pred_lib is not None:
+        return _pred_lib
+    with _lock:
+        if _pred_lib is None:
+            if not os.path.exists(PRED_LIB_PATH):
+                raise NativeLibraryError(
+                    f"predicted-ego library not built: {PRED_LIB_PATH} is missing (run "
+                    f"__graft_entry__.build())")
+            try:
+                handle = ctypes.CDLL(PRED_LIB_PATH)
+            except OSError as exc:  # pragma: no cover - depends on the ROCm install
+                raise NativeLibraryError(f"cannot load {PRED_LIB_PATH}: {exc}") from exc
+            i64, i32, dbl, u64, ptr = (ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                                       ctypes.c_uint64, ctypes.c_void_p)
+            handle.drcvar_sampled_halfspaces_f64_pred.argtypes = [
+                ptr, i64, i64, i64, i64, i64, i64, i64, i64, dbl, dbl, dbl, u64, ptr, i32,
+                i64, ptr, ptr, i64, i32, ptr, i32, dbl, dbl, dbl, dbl, dbl, ptr, ptr, ptr]
+            handle.drcvar_sampled_halfspaces_f64_pred.restype = ctypes.c_int
+            _pred_lib = handle
+    return _pred_lib
 
 
 def check(code: int) -> None:

@@ -26,10 +26,14 @@
 //
 // samples_out (optional): the kernel also stores the samples it drew; the record is the same bits.
 //
-// Two entries, one kernel template: drcvar_sampled_halfspaces_f64 freezes the stream offset and the
-// window in its arguments; drcvar_sampled_halfspaces_f64_dev (DEV below) reads the offset and the
-// window's first path row from a 16-byte state in device memory, so that a receding-horizon loop
-// can be replayed from one graph with a fresh draw per step (simulation/closed_loop.py).
+// Three entries, one kernel template: drcvar_sampled_halfspaces_f64 freezes the stream offset and
+// the window in its arguments; drcvar_sampled_halfspaces_f64_dev (DEV below) reads the offset and
+// the window's first path row from a 16-byte state in device memory, so that a receding-horizon
+// loop can be replayed from one graph with a fresh draw per step (simulation/closed_loop.py);
+// drcvar_sampled_halfspaces_f64_pred (PRED below) is the device-state form whose ego is each
+// problem's own predicted path.  The source is compiled twice: into the engine library with the
+// first two entries, and with DRCVAR_LOOP_PRED_LIBRARY into a library of its own
+// (include/drcvar_loop_pred.h) that holds the third and instantiates only the PRED kernels.
 //
 // The draw is the sampler's (drcvar_generator.inc) and the selection the stored form's
 // (drcvar_selection.inc); the direction alone differs on purpose, by one more Newton step of the
@@ -42,6 +46,9 @@
 #include <type_traits>
 
 #include "drcvar_sampling.h"
+#ifdef DRCVAR_LOOP_PRED_LIBRARY
+#include "drcvar_loop_pred.h"
+#endif
 
 namespace {
 
@@ -80,6 +87,7 @@ __device__ __forceinline__ void store_record(double* rec, double mux, double muy
 //   LOG_NB   log2 of the histogram bins
 //   ISO      the sampler's isotropic LogScale form
 //   DEV      the device-state form (below)
+//   PRED     the device-state form with a predicted ego (below; implies DEV)
 // Blocks of 512 threads are held to 128 VGPRs (four waves per SIMD): two workgroups share a CU,
 // so one unit's draw (VALU) overlaps the other's selection (barriers, LDS, one ranking wave).
 //
@@ -98,19 +106,45 @@ __device__ __forceinline__ void store_record(double* rec, double mux, double muy
 // writes `state`, so no finer ordering is needed.  PhiloxUniform is then made here, in scalar code
 // (one 32 x 32 -> 64 product, three xors), by the make_philox_uniform the host uses; a.pu arrives
 // with the key.
+//
+// The predicted-ego form (PRED, drcvar_sampled_halfspaces_f64_pred): the launch covers B problems
+// of O obstacles each, unit u = (b O + o) T + t, and the ego of a unit is its own problem's:
+// xs = x0[b] at t = 0, else pred[b, min(t + shift, pred_last)], ego = c_out xs (an fma chain over
+// the states from +0.0, as drcvar_loop_clearance_f64 forms it).  Everything else is DEV's, so the
+// launch is the base form on the gathered window with that ego.  b = (u / T) / O is uniform over
+// the workgroup: x0 and pred are uniform loads of const __restrict__ arguments, written by earlier
+// launches on the same stream (the solver, the advance kernel) and never by this one: the
+// visibility argument is `state`'s.  The row is clamped to [0, pred_last] for every t and shift;
+// b < B is the host's check of the unit window against B O T.  The ego is formed here, before
+// barrier 0 and blocks away from the direction's mu - ego: next to it the compiler contracted that
+// subtraction differently from the other forms (an ulp of h in 3 units of 24, seen by the bitwise
+// tests).  Measured and not kept: the row as one vector load per wave with
+// readlane in place of the nx scalar loads, 0.322 -> 0.336 ms per launch at B = 1024, N = 20.
 // ---------------------------------------------------------------------------------------------
+constexpr int kMaxStates = 8;  // DRCVAR_MPC_MAX_STATES
 struct NoState {};
 struct DevState {
   const drcvar_step_state* __restrict__ state;
   int64_t path_last;
 };
+struct PredState {
+  const drcvar_step_state* __restrict__ state;
+  int64_t path_last;
+  const double* __restrict__ x0;    // [B, nx]
+  const double* __restrict__ pred;  // [B, pred_last + 1, nx]
+  int64_t O, pred_last;             // obstacles per problem; the last row of pred
+  int nx, shift;
+  double cx[kMaxStates], cy[kMaxStates];  // c_out's two rows, zero past nx
+};
 
-template <int BLOCK, int PP, int LOG_NB, bool ISO, bool DEV = false>
+template <int BLOCK, int PP, int LOG_NB, bool ISO, bool DEV = false, bool PRED = false>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BLOCK >= 512 ? 4 : 1)))
 sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __restrict__ ego,
                          DrawArgs a, Params prm, double* __restrict__ out,
                          int32_t* __restrict__ status, double* __restrict__ samples_out,
-                         std::conditional_t<DEV, DevState, NoState> dev) {
+                         std::conditional_t<PRED, PredState,
+                                            std::conditional_t<DEV, DevState, NoState>> dev) {
+  static_assert(DEV || !PRED, "the predicted-ego form is a device-state form");
   constexpr int NW = BLOCK / kWave;
   constexpr int NB = 1 << LOG_NB;
   constexpr int Q = 2 * PP;  // sample slots per thread: 2 j the pair's first, 2 j + 1 its second
@@ -148,8 +182,26 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
   }
   const double* nom = nominal + o * a.nom_so + r * a.nom_st;
   const double nx = nom[0], ny = nom[1];
-  const double* ep = ego + r * a.ego_st;
-  const double e0 = ep[0], e1 = ep[1];
+  double e0, e1;
+  if constexpr (PRED) {
+    const int64_t b = o / dev.O;
+    const int64_t pr = t + dev.shift > dev.pred_last ? dev.pred_last : t + dev.shift;
+    const double* xs = (t == 0 ? dev.x0 + b * dev.nx
+                               : dev.pred + (b * (dev.pred_last + 1) + pr) * dev.nx);
+    e0 = e1 = 0.0;
+#pragma unroll
+    for (int j = 0; j < kMaxStates; ++j) {
+      if (j < dev.nx) {
+        const double xj = xs[j];
+        e0 = fma(dev.cx[j], xj, e0);
+        e1 = fma(dev.cy[j], xj, e1);
+      }
+    }
+  } else {
+    const double* ep = ego + r * a.ego_st;
+    e0 = ep[0];
+    e1 = ep[1];
+  }
   const int n = a.n;
   const int pairs = (n + 1) >> 1;  // Philox calls per unit
   const bool noisy = !(a.zero_first && t == 0);  // uniform: the noise-free first step draws nothing
@@ -358,11 +410,20 @@ struct Launch {
   int64_t count;
   bool iso;
   hipStream_t stream;
+  PredState pred;  // the predicted-ego form's arguments (state and path_last filled at launch)
 };
 
 template <int BLOCK, int PP, int LOG_NB, bool ISO>
 void launch_form(const Launch& L) {
   const dim3 grid(static_cast<unsigned>(L.count)), block(BLOCK);
+#ifdef DRCVAR_LOOP_PRED_LIBRARY
+  // this library launches the predicted-ego form alone: the only kernels it instantiates
+  PredState ps = L.pred;
+  ps.state = L.state;
+  ps.path_last = L.path_last;
+  hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true, true>), grid, block, 0,
+                     L.stream, L.nominal, nullptr, L.a, L.prm, L.out, L.status, nullptr, ps);
+#else
   if (L.state)
     hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true>), grid, block, 0,
                        L.stream, L.nominal, L.ego, L.a, L.prm, L.out, L.status, nullptr,
@@ -371,6 +432,7 @@ void launch_form(const Launch& L) {
     hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, false>), grid, block, 0,
                        L.stream, L.nominal, L.ego, L.a, L.prm, L.out, L.status, L.samples_out,
                        NoState{});
+#endif
 }
 
 template <int BLOCK, int PP, int LOG_NB>
@@ -382,9 +444,10 @@ void launch_plan(Launch L) {
     launch_form<BLOCK, PP, LOG_NB, false>(L);
 }
 
-// Both entries: the host checks, the launch-uniform arguments and the plan's launch.  `state`
+// Every entry: the host checks, the launch-uniform arguments and the plan's launch.  `state`
 // non-null selects the device-state form (n_steps is then the window length, path_steps the rows
-// of nominal and ego; stream_offset is unused, the kernel loads it).
+// of nominal and ego; stream_offset is unused, the kernel loads it).  `pred` non-null: the
+// predicted-ego form, which has no `ego`.
 int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_steps, int64_t nom_so,
                        int64_t nom_st, int64_t unit_begin, int64_t unit_count, int64_t n_samples,
                        double l00, double l10, double l11, uint64_t seed, uint64_t stream_offset,
@@ -392,7 +455,7 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
                        int32_t zero_first_step, const double* ego, int64_t ego_stride,
                        double robot_radius, double obstacle_radius, double alpha, double delta,
                        double epsilon, double* out, int32_t* status, double* samples_out, int64_t su,
-                       int64_t sn, void* stream) {
+                       int64_t sn, void* stream, const PredState* pred = nullptr) {
   if (n_obstacles < 0 || n_steps < 0 || n_samples < 0 || unit_begin < 0 || unit_count < 0)
     return DRCVAR_ERR_INVALID_ARGUMENT;
   if (dev && path_steps < 1) return DRCVAR_ERR_INVALID_ARGUMENT;
@@ -406,7 +469,7 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
   const int64_t units = n_obstacles * n_steps;
   if (unit_begin > units || unit_count > units - unit_begin) return DRCVAR_ERR_INVALID_ARGUMENT;
   if (unit_count == 0 || n_samples == 0) return DRCVAR_OK;
-  if (!nominal || !ego || !out) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (!nominal || (!ego && !pred) || !out) return DRCVAR_ERR_INVALID_ARGUMENT;
   if (dev && (!state || reinterpret_cast<uintptr_t>(state) % 16 != 0))
     return DRCVAR_ERR_INVALID_ARGUMENT;
   if (unit_count > 0x7fffffffLL) return DRCVAR_ERR_UNSUPPORTED;  // one workgroup per unit: grid x
@@ -443,6 +506,7 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
   L.path_last = path_steps - 1;
   L.count = unit_count;
   L.stream = static_cast<hipStream_t>(stream);
+  if (pred) L.pred = *pred;
   (void)hipGetLastError();  // clear stale errors from unrelated work
   switch (pick_plan(n_samples)) {
     case 0: launch_plan<64, 1, 7>(L); break;
@@ -459,6 +523,41 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
 
 }  // namespace
 
+#ifdef DRCVAR_LOOP_PRED_LIBRARY
+extern "C" int drcvar_sampled_halfspaces_f64_pred(
+    const double* nominal_path, int64_t n_obstacles, int64_t path_steps, int64_t nom_so,
+    int64_t nom_st, int64_t n_steps, int64_t unit_begin, int64_t unit_count, int64_t n_samples,
+    double l00, double l10, double l11, uint64_t seed, const drcvar_step_state* state,
+    int32_t zero_first_step, int64_t n_obstacles_per_problem, const double* x0, const double* pred,
+    int64_t pred_rows, int32_t n_states, const double* c_out, int32_t shift, double robot_radius,
+    double obstacle_radius, double alpha, double delta, double epsilon, double* out,
+    int32_t* status, void* stream) {
+  if (n_states < 1 || n_states > kMaxStates || n_obstacles_per_problem < 1 || pred_rows < 1 ||
+      (shift != 0 && shift != 1))
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  // whole problems: b = (u / T) / O must stay below the rows of x0 and pred
+  if (n_obstacles > 0 && n_obstacles % n_obstacles_per_problem != 0)
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  PredState ps{};
+  const bool launches = unit_count > 0 && n_samples > 0;
+  if (launches && (!x0 || !pred || !c_out)) return DRCVAR_ERR_INVALID_ARGUMENT;
+  ps.x0 = x0;
+  ps.pred = pred;
+  ps.O = n_obstacles_per_problem;
+  ps.pred_last = pred_rows - 1;
+  ps.nx = n_states;
+  ps.shift = shift;
+  if (launches)
+    for (int j = 0; j < n_states; ++j) {  // copied at call time: c_out is host memory
+      ps.cx[j] = c_out[j];
+      ps.cy[j] = c_out[n_states + j];
+    }
+  return sampled_halfspaces(nominal_path, n_obstacles, n_steps, nom_so, nom_st, unit_begin,
+                            unit_count, n_samples, l00, l10, l11, seed, 0, state, true, path_steps,
+                            zero_first_step, nullptr, 0, robot_radius, obstacle_radius, alpha, delta,
+                            epsilon, out, status, nullptr, 0, 0, stream, &ps);
+}
+#else
 extern "C" int drcvar_sampled_launch_plan(int64_t n_samples, int32_t* threads,
                                           int32_t* pairs_per_thread) {
   if (n_samples < 1) return DRCVAR_ERR_INVALID_ARGUMENT;
@@ -494,3 +593,4 @@ extern "C" int drcvar_sampled_halfspaces_f64_dev(
                             zero_first_step, ego_path, ego_stride, robot_radius, obstacle_radius,
                             alpha, delta, epsilon, out, status, nullptr, 0, 0, stream);
 }
+#endif

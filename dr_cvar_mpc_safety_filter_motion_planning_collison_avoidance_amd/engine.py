@@ -13,6 +13,8 @@ These are the batched calls everything else is built on:
 * :func:`sampled_halfspaces_dev` — ``drcvar_sampled_halfspaces_f64_dev``: the same launch with the
   window start and the stream offset read from a device-resident state, for a receding-horizon
   loop replayed from one graph (``simulation/closed_loop.py``).
+* :func:`sampled_halfspaces_pred` — ``drcvar_sampled_halfspaces_f64_pred``: that launch for a
+  batch of loops, each unit's ego taken from its own problem's state and predicted path.
 
 All enqueue one kernel on the current HIP stream and return without synchronising.  Inputs must
 be float64 CUDA tensors whose two coordinates are adjacent (last stride 1); any other strides are
@@ -387,6 +389,105 @@ def sampled_halfspaces_dev(nominal_path: torch.Tensor, ego_path: torch.Tensor, n
     :func:`prepare_sampled_halfspaces_dev`): the halfspaces of the window that ``state`` names."""
     launch, out = prepare_sampled_halfspaces_dev(nominal_path, ego_path, n_steps, n_samples, params,
                                                  state, **kwargs)
+    if out.numel() > 0:
+        launch()
+    return out
+
+
+def prepare_sampled_halfspaces_pred(nominal_path: torch.Tensor, x0: torch.Tensor, pred: torch.Tensor,
+                                    c_out, n_obstacles: int, n_steps: int, n_samples: int,
+                                    params: RiskParams, state: torch.Tensor, *, shift: int = 1,
+                                    noise_cov=DEFAULT_NOISE_COV, seed: int = 0,
+                                    zero_first_step: bool = True, unit_begin: int = 0,
+                                    unit_count: int | None = None, out: torch.Tensor | None = None,
+                                    status: torch.Tensor | None = None, stream=None,
+                                    chol=None) -> tuple[PreparedLaunch, torch.Tensor]:
+    """Freeze one ``drcvar_sampled_halfspaces_f64_pred`` call (``include/drcvar_loop_pred.h``):
+    :func:`prepare_sampled_halfspaces_dev` for B problems of ``n_obstacles`` = O obstacles each,
+    with the ego of every unit taken from its own problem's state and predicted path instead of
+    one shared ego path.
+
+    nominal_path ``[B O, P, 2]`` (problem b's obstacles are rows ``b O .. b O + O - 1``), x0 ``[B,
+    nx]`` and pred ``[B, R, nx]`` (``R >= 1``, ``1 <= nx <= 8``) are float64 device tensors, x0 and
+    pred contiguous; ``c_out`` is a host ``[2, nx]`` array, copied when this function is called.
+    Unit ``u = (b O + o) T + t`` draws what :func:`sampled_halfspaces_dev` draws and takes the ego
+    ``c_out @ xs`` (an fma chain from +0.0), ``xs = x0[b]`` at ``t = 0`` and ``pred[b, min(t +
+    shift, R - 1)]`` after it, ``shift`` 0 or 1: x0, pred and ``state`` are read from device memory
+    when the kernel runs, so a captured launch follows them.  Per problem the records and status
+    words are bit for bit those of :func:`sampled_halfspaces` on the gathered window with that ego,
+    ``unit_begin = b O T``, ``unit_count = O T`` and the state's offset.  ``out`` is ``[B O,
+    n_steps, 8]``, or ``[unit_count, 8]`` for a unit window; ``status``, ``stream`` and ``chol`` as
+    in :func:`prepare_sampled_halfspaces_dev`."""
+    params.validate()
+    if not isinstance(nominal_path, torch.Tensor) or nominal_path.dim() != 3 or nominal_path.shape[0] < 1:
+        raise ValueError("nominal_path must be float64 [B O, P, 2] with B O, P >= 1")
+    check_path(nominal_path, "nominal_path", (None, None, 2))
+    dev = nominal_path.device
+    BO, P, _ = nominal_path.shape
+    O = int(n_obstacles)
+    if O < 1 or BO % O != 0:
+        raise ValueError(f"n_obstacles={O} must be at least 1 and divide nominal_path's {BO} rows")
+    B = BO // O
+    if not isinstance(x0, torch.Tensor) or x0.dim() != 2:
+        raise ValueError("x0 must be a float64 [B, nx] tensor")
+    nx = x0.shape[1]
+    if not 1 <= nx <= _native.MPC_MAX_STATES:
+        raise ValueError(f"x0 has {nx} states, outside 1..{_native.MPC_MAX_STATES}")
+    check_path(x0, "x0", (B, nx), dev)
+    if not isinstance(pred, torch.Tensor) or pred.dim() != 3:
+        raise ValueError("pred must be a float64 [B, R, nx] tensor")
+    check_path(pred, "pred", (B, None, nx), dev)
+    if not x0.is_contiguous() or not pred.is_contiguous():
+        raise ValueError("x0 and pred must be contiguous")
+    import numpy as np
+    c = np.ascontiguousarray(np.asarray(c_out, dtype=np.float64))
+    if c.shape != (2, nx):
+        raise ValueError(f"c_out must have shape (2, {nx}), got {c.shape}")
+    if int(shift) not in (0, 1):
+        raise ValueError(f"shift={shift} must be 0 or 1")
+    check_step_state(state, dev)
+    T, n = int(n_steps), int(n_samples)
+    if T < 0:
+        raise ValueError(f"n_steps={T} must not be negative")
+    if n < 1 or n > _native.MAX_SAMPLES:
+        raise ValueError(f"n_samples={n} outside 1..{_native.MAX_SAMPLES}")
+    whole = unit_count is None
+    u0 = int(unit_begin)
+    count = BO * T - u0 if whole else int(unit_count)
+    if u0 < 0 or count < 0 or u0 + count > BO * T:
+        raise ValueError(f"unit range [{u0}, {u0 + count}) outside the {BO} x {T} grid")
+    whole = whole and u0 == 0
+    shape = (BO, T, OUT_WIDTH) if whole else (count, OUT_WIDTH)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=dev)
+    else:
+        _check_out(out, shape, dev, "[B O, T, 8]" if whole else "[units, 8]")
+    if status is not None:
+        _check_status(status, count, dev)
+    l00, l10, l11 = _noise_factor(noise_cov, chol)
+    args = (ctypes.c_void_p(nominal_path.data_ptr()), BO, P, nominal_path.stride(0),
+            nominal_path.stride(1), T, u0, count, n, l00, l10, l11,
+            ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), ctypes.c_void_p(state.data_ptr()),
+            ctypes.c_int32(1 if zero_first_step else 0), O,
+            ctypes.c_void_p(x0.data_ptr()), ctypes.c_void_p(pred.data_ptr()), pred.shape[1],
+            ctypes.c_int32(nx), ctypes.c_void_p(c.ctypes.data), ctypes.c_int32(int(shift)),
+            params.robot_radius, params.obstacle_radius, params.alpha, params.delta, params.epsilon,
+            ctypes.c_void_p(out.data_ptr()),
+            ctypes.c_void_p(status.data_ptr() if status is not None else None),
+            ctypes.c_void_p(_stream_handle(dev, stream)))
+    launch = PreparedLaunch(_native.pred_lib().drcvar_sampled_halfspaces_f64_pred, args,
+                            (nominal_path, x0, pred, c, state, out, status))
+    return launch, out
+
+
+def sampled_halfspaces_pred(nominal_path: torch.Tensor, x0: torch.Tensor, pred: torch.Tensor, c_out,
+                            n_obstacles: int, n_steps: int, n_samples: int, params: RiskParams,
+                            state: torch.Tensor, **kwargs) -> torch.Tensor:
+    """One ``drcvar_sampled_halfspaces_f64_pred`` launch (arguments:
+    :func:`prepare_sampled_halfspaces_pred`): the halfspaces of the window that ``state`` names,
+    each problem's about its own state and predicted path."""
+    launch, out = prepare_sampled_halfspaces_pred(nominal_path, x0, pred, c_out, n_obstacles,
+                                                  n_steps, n_samples, params, state, **kwargs)
     if out.numel() > 0:
         launch()
     return out

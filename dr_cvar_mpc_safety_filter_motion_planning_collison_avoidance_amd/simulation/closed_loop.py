@@ -17,11 +17,19 @@ so a captured step carries no frozen per-step quantity and ``run`` replays one g
 step (or per ``steps_per_graph`` steps) with no host work in between.  Exact semantics:
 ``include/drcvar_mpc.h`` (``drcvar_mpc_step_advance_f64``) and DESIGN.md §5.3.
 
-The halfspaces are computed about the REFERENCE path (``ego_path = x_ref_path @ C.T``), as the
-reference does (``main.py:95-97``), not about the actual state.  One problem per loop;
-:class:`RecedingHorizonBatch` advances B loops in lockstep with the same three launches per step
-(``drcvar_mpc_step_advance_batch_f64``, ``include/drcvar_loop.h``: one workgroup and one device state per problem, DESIGN.md
-§5.4).
+By default (``linearize="reference"``) the halfspaces are computed about the REFERENCE path
+(``ego_path = x_ref_path @ C.T``), as the reference does for its one window (``main.py:95-97``),
+not about the actual state.  With ``linearize="predicted"`` the halfspace launch is
+``drcvar_sampled_halfspaces_f64_pred`` (``include/drcvar_loop_pred.h``) and every
+loop's halfspaces are taken about its OWN motion: window row 0 about the state actually reached
+(disturbance included), row t >= 1 about the previous step's predicted state for the same path
+time (the solver's ``x_out``, shifted by one row; the rolled-out fallback after a failed solve;
+the reference path on the first step after ``reset``).  ``relinearize=r`` then repeats
+(halfspaces about the answer just written, solve) r times before the advance, on the same draws:
+a control step is ``3 + 2 r`` launches, still one linear chain.  One problem per loop;
+:class:`RecedingHorizonBatch` advances B loops in lockstep with the same launches per step
+(``drcvar_mpc_step_advance_batch_f64``, ``include/drcvar_loop.h``: one workgroup and one device
+state per problem).
 
 Both classes take ``evaluate=LoopEvaluation(...)``: a fourth launch per control step
 (``drcvar_loop_clearance_f64``, ``include/drcvar_loop_eval.h``) then holds the state just reached
@@ -44,6 +52,7 @@ from ..engine import DEFAULT_NOISE_COV
 from .obstacles import NOISE_COV
 
 BACKENDS = ("graph", "launches", "reference")
+LINEARIZE = ("reference", "predicted")
 _MASK64 = 2 ** 64 - 1
 _MIN_LOG_ROWS = 64
 
@@ -266,7 +275,69 @@ class _Evaluated:
         return result
 
 
-class RecedingHorizonFilter(_Evaluated):
+def check_linearize(linearize, relinearize):
+    """The ``linearize=`` / ``relinearize=`` arguments of the loop classes (host only)."""
+    if linearize not in LINEARIZE:
+        raise ValueError(f"linearize must be one of {LINEARIZE}, got {linearize!r}")
+    if isinstance(relinearize, bool) or int(relinearize) != relinearize or int(relinearize) < 0:
+        raise ValueError(f"relinearize={relinearize!r} must be a non-negative integer")
+    if int(relinearize) > 0 and linearize != "predicted":
+        raise ValueError('relinearize > 0 needs linearize="predicted"')
+
+
+class _Linearized:
+    """What the two loop classes share for ``linearize="predicted"``: the
+    halfspaces of window row t are taken about the loop's own prediction for that path time
+    instead of the reference path (``drcvar_sampled_halfspaces_f64_pred``,
+    ``include/drcvar_loop_pred.h``).  The single class is the batch of one problem here."""
+
+    linearize, relinearize = "reference", 0
+
+    def _lin_init(self, linearize, relinearize, n_problems, n_obstacles, nominal_flat):
+        self.linearize, self.relinearize = linearize, int(relinearize)
+        self._lin_B, self._lin_O, self._lin_nominal = n_problems, n_obstacles, nominal_flat
+        C = torch.as_tensor(self.model.C, dtype=torch.float64).reshape(2, self.model.nx)
+        self._lin_C = C.contiguous().numpy()          # host memory: copied into each launch
+        self._lin_C_dev = C.to(self.model.device)
+
+    def _lin_prime(self):
+        """``reset``: the prediction the first step linearises about is the reference path, row j
+        of ``x_out`` holding ``x_ref_path[c(step - 1 + j)]`` (``shift = 1`` reads row t + 1)."""
+        if self.linearize == "predicted":
+            self._x.copy_(self._window(self.x_ref_path, self._step - 1, self.model.horizon + 1))
+
+    def _lin_launch(self, stream, shift):
+        """The halfspace launch of a captured step about (``x0``, ``x_out``)."""
+        return engine.prepare_sampled_halfspaces_pred(
+            self._lin_nominal, self._x0.view(self._lin_B, -1), self._x, self._lin_C, self._lin_O,
+            self.model.horizon, self.n_samples, self.params, self._state.view(-1, 2)[0],
+            shift=shift, noise_cov=self.noise_cov, seed=self.seed,
+            zero_first_step=self.zero_first_step, out=self._record, stream=stream, chol=self.chol)[0]
+
+    def _lin_reference_record(self, window, shift):
+        """The same record ``[B O, H, 8]`` from entries that predate the predicted form: per
+        problem the ego is formed by a torch multiply-and-add chain over the states (from +0.0, in
+        the kernel's order) and ``engine.sampled_halfspaces`` runs on the problem's unit window.
+        Bitwise the kernel's fma chain when every product ``c_out[i, j] * x[j]`` is exact (a
+        selector ``C``, the reference's model, or power-of-two entries); otherwise it agrees to an
+        ulp of the ego."""
+        H, B, O = self.model.horizon, self._lin_B, self._lin_O
+        rows = (self._rows[H] + shift).clamp_(max=H)
+        records = []
+        for b in range(B):
+            xs = self._x[b].index_select(0, rows)                 # [H, nx]: pred[b, min(t + shift, H)]
+            xs[0].copy_(self._x0.view(B, -1)[b])                  # t = 0: the state actually reached
+            ego = torch.zeros((H, 2), dtype=torch.float64, device=xs.device)
+            for j in range(xs.shape[1]):
+                ego = ego + xs[:, j:j + 1] * self._lin_C_dev[:, j]
+            records.append(engine.sampled_halfspaces(
+                window, ego, self.n_samples, self.params, noise_cov=self.noise_cov, chol=self.chol,
+                seed=self.seed, stream_offset=self._offset, zero_first_step=self.zero_first_step,
+                unit_begin=b * O * H, unit_count=O * H))
+        return torch.cat(records).view(B * O, H, engine.OUT_WIDTH)
+
+
+class RecedingHorizonFilter(_Evaluated, _Linearized):
     """One problem's receding-horizon loop.
 
     ``nominal_path [O, P, 2]`` (obstacles), ``x_ref_path [P, nx]`` and ``u_ref_path [P, nu]`` are
@@ -283,17 +354,26 @@ class RecedingHorizonFilter(_Evaluated):
     same three launches issued eagerly) and ``"reference"`` (the semantics spelled out with
     ``engine.sampled_halfspaces`` on gathered windows, ``filter_batch`` and torch ops; the tests'
     yardstick; it also fills ``reference_trace`` with each step's solver outputs).
+
+    ``linearize="predicted"`` takes the halfspaces about the loop's own state and predicted path
+    (module docstring) and ``relinearize=r`` adds r passes of (halfspaces about the
+    answer just written, solve) per step, all on the step's draws; the logged ``info`` is the last
+    pass's.  Its ``reference`` backend forms the ego by a torch multiply-and-add chain, which is
+    bitwise the kernel's fma chain when every product ``C[i, j] x[j]`` is exact (a selector ``C``,
+    power-of-two entries) and agrees to an ulp of the ego otherwise.
     """
 
     def __init__(self, model: MPCModel, nominal_path, x_ref_path, u_ref_path, n_samples, params, *,
                  metric="dr_cvar", noise_cov=DEFAULT_NOISE_COV, chol=None, seed=0,
                  zero_first_step=True, max_iter=DEFAULT_MAX_ITER, tol=DEFAULT_TOL, polish=True,
-                 options=None, disturbance=None, steps_per_graph=1, evaluate=None):
+                 options=None, disturbance=None, steps_per_graph=1, evaluate=None,
+                 linearize="reference", relinearize=0):
         if metric not in METRIC_COLUMNS:
             raise ValueError(f"metric must be one of {tuple(METRIC_COLUMNS)}, got {metric!r}")
         if int(steps_per_graph) < 1:
             raise ValueError(f"steps_per_graph={steps_per_graph} must be at least 1")
         check_evaluate(evaluate)
+        check_linearize(linearize, relinearize)
         n = int(n_samples)
         if n < 1 or n > _native.MAX_SAMPLES:
             raise ValueError(f"n_samples={n} outside 1..{_native.MAX_SAMPLES}")
@@ -340,6 +420,7 @@ class RecedingHorizonFilter(_Evaluated):
         self._workspace = torch.empty(max(model.workspace_doubles(1, O), 1), **f64)
         self._rows = {k: torch.arange(k, device=dev) for k in (H, H + 1)}
         self._eval_init(evaluate, 1, O, nominal_path)
+        self._lin_init(linearize, relinearize, 1, O, nominal_path)
         self._logs = None           # (x_log [cap + 1, nx], u_log [cap, nu], info_log [cap, 10])
         self._cap, self._step_begin = 0, 0
         self._primed = False
@@ -368,6 +449,7 @@ class RecedingHorizonFilter(_Evaluated):
         self._u_fb[0].copy_(self._window(self.u_ref_path, self._step, H))
         self._last_u.zero_()
         self._have_last.zero_()
+        self._lin_prime()
         self._primed = True
         cap = max(self._cap, _MIN_LOG_ROWS) if self.disturbance is None else self.disturbance.shape[0]
         if self._logs is not None and cap == self._cap and self._step == self._step_begin:
@@ -399,10 +481,15 @@ class RecedingHorizonFilter(_Evaluated):
     def _make_step(self, stream):
         m = self.model
         H = m.horizon
-        halfspaces, _ = engine.prepare_sampled_halfspaces_dev(
-            self.nominal_path, self.ego_path, H, self.n_samples, self.params, self._state,
-            noise_cov=self.noise_cov, seed=self.seed, zero_first_step=self.zero_first_step,
-            out=self._record, stream=stream, chol=self.chol)
+        again = None
+        if self.linearize == "predicted":
+            halfspaces = self._lin_launch(stream, 1)
+            again = self._lin_launch(stream, 0) if self.relinearize else None
+        else:
+            halfspaces, _ = engine.prepare_sampled_halfspaces_dev(
+                self.nominal_path, self.ego_path, H, self.n_samples, self.params, self._state,
+                noise_cov=self.noise_cov, seed=self.seed, zero_first_step=self.zero_first_step,
+                out=self._record, stream=stream, chol=self.chol)
         hs_h, hs_g = record_views(self._record, self.metric)
         vp = ctypes.c_void_p
         x_log, u_log, info_log = self._logs
@@ -420,11 +507,19 @@ class RecedingHorizonFilter(_Evaluated):
         # state just reached and state.step its path row); the chain stays linear
         evaluation = self._eval_launch(stream) if self.evaluate is not None else None
 
-        def step():
-            halfspaces()
+        def solve():
             filter_batch(m, hs_h, hs_g, self._x0, self._x_ref_win, self._u_fb, self.max_iter,
                          self.tol, self.polish, workspace=self._workspace, stream=stream,
                          options=self.options, out=out)
+
+        def step():
+            halfspaces()
+            solve()
+            # relinearize: the same draws (the state moves only in the advance) about the answer
+            # just written, then the solve again; still one linear chain
+            for _ in range(self.relinearize):
+                again()
+                solve()
             advance()
             if evaluation is not None:
                 evaluation()
@@ -432,8 +527,10 @@ class RecedingHorizonFilter(_Evaluated):
 
     def _mutable(self):
         evaluated = [] if self.evaluate is None else [self._min_d2, self._eval_hits]
+        # (under "predicted" x_out is an input of the next step's halfspaces)
+        predicted = [self._x] if self.linearize == "predicted" else []
         return [self._state, self._x0, self._x_ref_win, self._u_fb, self._last_u, self._have_last,
-                *self._logs, *evaluated]
+                *self._logs, *evaluated, *predicted]
 
     def _capture(self):
         return _capture_chain(self.model.device, self._make_step, self._mutable, self.steps_per_graph)
@@ -445,14 +542,19 @@ class RecedingHorizonFilter(_Evaluated):
         s = self._step
         window = self.nominal_path.index_select(
             1, (self._rows[H] + s).clamp_(0, self.path_steps - 1))
-        ego_window = self._window(self.ego_path, s, H)
-        record = engine.sampled_halfspaces(window, ego_window, self.n_samples, self.params,
-                                           noise_cov=self.noise_cov, chol=self.chol, seed=self.seed,
-                                           stream_offset=self._offset,
-                                           zero_first_step=self.zero_first_step)
-        hs_h, hs_g = record_views(record[:, :H], self.metric)
-        x, u, info = filter_batch(m, hs_h, hs_g, self._x0, self._x_ref_win, self._u_fb,
-                                  self.max_iter, self.tol, self.polish, options=self.options)
+        for p in range(1 + self.relinearize):
+            if self.linearize == "predicted":
+                record = self._lin_reference_record(window, 1 if p == 0 else 0)
+            else:
+                ego_window = self._window(self.ego_path, s, H)
+                record = engine.sampled_halfspaces(window, ego_window, self.n_samples, self.params,
+                                                   noise_cov=self.noise_cov, chol=self.chol,
+                                                   seed=self.seed, stream_offset=self._offset,
+                                                   zero_first_step=self.zero_first_step)
+            hs_h, hs_g = record_views(record[:, :H], self.metric)
+            x, u, info = filter_batch(m, hs_h, hs_g, self._x0, self._x_ref_win, self._u_fb,
+                                      self.max_iter, self.tol, self.polish, options=self.options)
+            self._x.copy_(x)   # (the next linearisation point; the device backends' x_out)
         self.reference_trace.append((x[0].clone(), u[0].clone(), info[0].clone()))
         x_log, u_log, info_log = self._logs
         x_next = x[0, 1]
@@ -551,7 +653,7 @@ def batch_x0(x0, n_problems: int, nx: int) -> torch.Tensor:
     return x0
 
 
-class RecedingHorizonBatch(_Evaluated):
+class RecedingHorizonBatch(_Evaluated, _Linearized):
     """``n_problems`` receding-horizon loops that advance in lockstep: three launches per control
     step for any B.
 
@@ -569,10 +671,15 @@ class RecedingHorizonBatch(_Evaluated):
 
     Draws: problem b, obstacle o, window step t is unit ``(b O + o) H + t`` of the halfspace launch,
     so the problems get independent draws from the one ``seed`` and stream offset, and with B = 1
-    the loop is :class:`RecedingHorizonFilter`'s, bit for bit.  The records do not depend on
-    ``metric``: batches built with the same seed, offset and paths see the same halfspace records
-    at equal states, so mean, CVaR and DR-CVaR are compared on common random numbers by running
-    three batches (there is no per-problem metric).
+    the loop is :class:`RecedingHorizonFilter`'s, bit for bit.  With ``linearize="reference"`` the
+    records do not depend on ``metric``: batches built with the same seed, offset and paths see
+    the same halfspace records at equal steps, so mean, CVaR and DR-CVaR are compared on common
+    random numbers by running three batches (there is no per-problem metric).  With
+    ``linearize="predicted"`` (:class:`RecedingHorizonFilter`; step 1 is then
+    ``drcvar_sampled_halfspaces_f64_pred`` on ``x0 [B, nx]`` and ``x_out [B, H + 1, nx]``, and
+    problems that differ in ``x0`` or disturbance get different halfspaces) the records follow each
+    loop's own motion and therefore its metric; the DRAWS are still common random numbers across
+    batches with the same seed and offset.
 
     ``reset(x0)`` takes ``[B, nx]`` or ``[nx]``.  ``run(n, backend)`` returns ``(states [B, n + 1,
     nx], inputs [B, n, nu], info [B, n, 10])``; backends, log capacity, rebasing, the limit of D
@@ -585,12 +692,14 @@ class RecedingHorizonBatch(_Evaluated):
     def __init__(self, model: MPCModel, nominal_path, x_ref_path, u_ref_path, n_samples, params, *,
                  n_problems, metric="dr_cvar", noise_cov=DEFAULT_NOISE_COV, chol=None, seed=0,
                  zero_first_step=True, max_iter=DEFAULT_MAX_ITER, tol=DEFAULT_TOL, polish=True,
-                 options=None, disturbance=None, steps_per_graph=1, evaluate=None):
+                 options=None, disturbance=None, steps_per_graph=1, evaluate=None,
+                 linearize="reference", relinearize=0):
         if metric not in METRIC_COLUMNS:
             raise ValueError(f"metric must be one of {tuple(METRIC_COLUMNS)}, got {metric!r}")
         if int(steps_per_graph) < 1:
             raise ValueError(f"steps_per_graph={steps_per_graph} must be at least 1")
         check_evaluate(evaluate)
+        check_linearize(linearize, relinearize)
         n = int(n_samples)
         if n < 1 or n > _native.MAX_SAMPLES:
             raise ValueError(f"n_samples={n} outside 1..{_native.MAX_SAMPLES}")
@@ -633,6 +742,7 @@ class RecedingHorizonBatch(_Evaluated):
         self._workspace = torch.empty(max(model.workspace_doubles(B, O), 1), **f64)
         self._rows = {k: torch.arange(k, device=dev) for k in (H, H + 1)}
         self._eval_init(evaluate, B, O, self.nominal_path)
+        self._lin_init(linearize, relinearize, B, O, self.nominal_path)
         self._logs = None           # (x_log [B, cap + 1, nx], u_log [B, cap, nu], info_log [B, cap, 10])
         self._cap, self._step_begin = 0, 0
         self._primed = False
@@ -670,6 +780,7 @@ class RecedingHorizonBatch(_Evaluated):
         self._u_fb.copy_(self._window(self.u_ref_path, self._step, H))
         self._last_u.zero_()
         self._have_last.zero_()
+        self._lin_prime()
         self._primed = True
         cap = max(self._cap, _MIN_LOG_ROWS) if self.disturbance is None else self.disturbance.shape[1]
         if self._logs is not None and cap == self._cap and self._step == self._step_begin:
@@ -700,10 +811,15 @@ class RecedingHorizonBatch(_Evaluated):
     def _make_step(self, stream):
         m = self.model
         H = m.horizon
-        halfspaces, _ = engine.prepare_sampled_halfspaces_dev(
-            self.nominal_path, self.ego_path, H, self.n_samples, self.params, self._state[0],
-            noise_cov=self.noise_cov, seed=self.seed, zero_first_step=self.zero_first_step,
-            out=self._record, stream=stream, chol=self.chol)
+        again = None
+        if self.linearize == "predicted":
+            halfspaces = self._lin_launch(stream, 1)
+            again = self._lin_launch(stream, 0) if self.relinearize else None
+        else:
+            halfspaces, _ = engine.prepare_sampled_halfspaces_dev(
+                self.nominal_path, self.ego_path, H, self.n_samples, self.params, self._state[0],
+                noise_cov=self.noise_cov, seed=self.seed, zero_first_step=self.zero_first_step,
+                out=self._record, stream=stream, chol=self.chol)
         hs_h, hs_g = self._views(self._record)
         vp = ctypes.c_void_p
         x_log, u_log, info_log = self._logs
@@ -721,11 +837,19 @@ class RecedingHorizonBatch(_Evaluated):
         # state just reached and state.step its path row); the chain stays linear
         evaluation = self._eval_launch(stream) if self.evaluate is not None else None
 
-        def step():
-            halfspaces()
+        def solve():
             filter_batch(m, hs_h, hs_g, self._x0, self._x_ref_win, self._u_fb, self.max_iter,
                          self.tol, self.polish, workspace=self._workspace, stream=stream,
                          options=self.options, out=out)
+
+        def step():
+            halfspaces()
+            solve()
+            # relinearize: the same draws (the state moves only in the advance) about the answer
+            # just written, then the solve again; still one linear chain
+            for _ in range(self.relinearize):
+                again()
+                solve()
             advance()
             if evaluation is not None:
                 evaluation()
@@ -733,8 +857,10 @@ class RecedingHorizonBatch(_Evaluated):
 
     def _mutable(self):
         evaluated = [] if self.evaluate is None else [self._min_d2, self._eval_hits]
+        # (under "predicted" x_out is an input of the next step's halfspaces)
+        predicted = [self._x] if self.linearize == "predicted" else []
         return [self._state, self._x0, self._x_ref_win, self._u_fb, self._last_u, self._have_last,
-                *self._logs, *evaluated]
+                *self._logs, *evaluated, *predicted]
 
     # ---- the semantics, from the entry points that predate the loop -----------------------------
     def _reference_step(self, i):
@@ -743,14 +869,19 @@ class RecedingHorizonBatch(_Evaluated):
         s = self._step
         window = self.nominal_path.index_select(
             1, (self._rows[H] + s).clamp_(0, self.path_steps - 1))     # [B O, H, 2]
-        ego_window = self._window(self.ego_path, s, H)
-        record = engine.sampled_halfspaces(window, ego_window, self.n_samples, self.params,
-                                           noise_cov=self.noise_cov, chol=self.chol, seed=self.seed,
-                                           stream_offset=self._offset,
-                                           zero_first_step=self.zero_first_step)
-        hs_h, hs_g = self._views(record)
-        x, u, info = filter_batch(m, hs_h, hs_g, self._x0, self._x_ref_win, self._u_fb,
-                                  self.max_iter, self.tol, self.polish, options=self.options)
+        for p in range(1 + self.relinearize):
+            if self.linearize == "predicted":
+                record = self._lin_reference_record(window, 1 if p == 0 else 0)
+            else:
+                ego_window = self._window(self.ego_path, s, H)
+                record = engine.sampled_halfspaces(window, ego_window, self.n_samples, self.params,
+                                                   noise_cov=self.noise_cov, chol=self.chol,
+                                                   seed=self.seed, stream_offset=self._offset,
+                                                   zero_first_step=self.zero_first_step)
+            hs_h, hs_g = self._views(record)
+            x, u, info = filter_batch(m, hs_h, hs_g, self._x0, self._x_ref_win, self._u_fb,
+                                      self.max_iter, self.tol, self.polish, options=self.options)
+            self._x.copy_(x)   # (the next linearisation point; the device backends' x_out)
         self.reference_trace.append((x.clone(), u.clone(), info.clone()))
         x_log, u_log, info_log = self._logs
         x_next = x[:, 1]
