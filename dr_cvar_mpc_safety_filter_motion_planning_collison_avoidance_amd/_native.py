@@ -1,8 +1,9 @@
 """Loader for the HIP engine (``_lib/libdrcvar_halfspace.so``) — the C ABI of
 ``include/drcvar_halfspace.h`` (+ ``drcvar_mpc.h``, ``drcvar_sampling.h``, ``drcvar_exchange.h``)
 bound with ctypes; beside it the loop library (``drcvar_loop.h``, :func:`loop_lib`), the
-loop-evaluation library (``drcvar_loop_eval.h``, :func:`eval_lib`) and the predicted-ego library
-(``drcvar_loop_pred.h``, :func:`pred_lib`), one entry family each.
+loop-evaluation library (``drcvar_loop_eval.h``, :func:`eval_lib`), the predicted-ego library
+(``drcvar_loop_pred.h``, :func:`pred_lib`) and the risk-table library (``drcvar_loop_risk.h``,
+:func:`risk_lib`), one entry family each.
 
 There is deliberately no fallback: if the shared library is missing or cannot be loaded every
 entry point raises :class:`NativeLibraryError`.  ``build()`` compiles it for gfx950 in-tree.
@@ -48,6 +49,14 @@ PRED_LIB_PATH = os.path.join(LIB_DIR, "libdrcvar_loop_pred.so")
 PRED_HEADER = os.path.join(INCLUDE_DIR, "drcvar_loop_pred.h")
 PRED_UNIT = (os.path.join(PKG_DIR, "csrc", "drcvar_sampled.hip"), ("-DDRCVAR_LOOP_PRED_LIBRARY",))
 PRED_SYMBOLS = ("drcvar_sampled_halfspaces_f64_pred",)
+# The risk-table library (include/drcvar_loop_risk.h), by the same recipe: csrc/drcvar_sampled.hip
+# compiled a third time, with DRCVAR_LOOP_RISK_LIBRARY (14 kernels: the seven plans x ISO of the
+# risk-table form, none of the other two libraries').
+RISK_LIB_PATH = os.path.join(LIB_DIR, "libdrcvar_loop_risk.so")
+RISK_HEADER = os.path.join(INCLUDE_DIR, "drcvar_loop_risk.h")
+RISK_UNIT = (os.path.join(PKG_DIR, "csrc", "drcvar_sampled.hip"), ("-DDRCVAR_LOOP_RISK_LIBRARY",))
+RISK_SYMBOLS = ("drcvar_risk_table_row_bytes", "drcvar_risk_table_fill",
+                "drcvar_sampled_halfspaces_f64_risk")
 
 ABI_VERSION = 3
 OUT_WIDTH = 8
@@ -274,11 +283,11 @@ def build(verbose: bool = False, extra_flags=()) -> str:
     os.makedirs(obj_dir, exist_ok=True)
     import glob
     incs = sorted(glob.glob(os.path.join(PKG_DIR, "csrc", "*.inc")))  # tables the sources include
-    headers = b"".join(open(h, "rb").read() for h in HEADERS + [LOOP_HEADER, EVAL_HEADER, PRED_HEADER] + incs)
+    headers = b"".join(open(h, "rb").read() for h in HEADERS + [LOOP_HEADER, EVAL_HEADER, PRED_HEADER, RISK_HEADER] + incs)
     # the compiler's identity is part of every key: objects of an older hipcc / ROCm are rebuilt
     toolchain = _toolchain(probe=True)
     objs, procs = [], []
-    for src, defs in _compile_units() + [LOOP_UNIT, EVAL_UNIT, PRED_UNIT]:
+    for src, defs in _compile_units() + [LOOP_UNIT, EVAL_UNIT, PRED_UNIT, RISK_UNIT]:
         flags = _unit_flags(defs, extra_flags)
         key = hashlib.sha256(open(src, "rb").read() + headers + toolchain
                              + " ".join(flags).encode()).hexdigest()[:16]
@@ -296,9 +305,11 @@ def build(verbose: bool = False, extra_flags=()) -> str:
         raise subprocess.CalledProcessError(1, failed[0])
     for _, obj, _ in procs:
         os.replace(obj + ".tmp", obj)
-    # (LOOP_UNIT, EVAL_UNIT and PRED_UNIT are the last three: each is a library of its own)
-    for path, members in ((LIB_PATH, objs[:-3]), (LOOP_LIB_PATH, objs[-3:-2]),
-                          (EVAL_LIB_PATH, objs[-2:-1]), (PRED_LIB_PATH, objs[-1:])):
+    # (LOOP_UNIT, EVAL_UNIT, PRED_UNIT and RISK_UNIT are the last four: each is a library of its
+    # own)
+    for path, members in ((LIB_PATH, objs[:-4]), (LOOP_LIB_PATH, objs[-4:-3]),
+                          (EVAL_LIB_PATH, objs[-3:-2]), (PRED_LIB_PATH, objs[-2:-1]),
+                          (RISK_LIB_PATH, objs[-1:])):
         link = ["hipcc", f"--offload-arch={OFFLOAD_ARCH}", "-shared", "-fPIC", *members,
                 "-o", path + ".tmp"]
         if verbose:
@@ -518,6 +529,40 @@ def pred_lib():
             handle.drcvar_sampled_halfspaces_f64_pred.restype = ctypes.c_int
             _pred_lib = handle
     return _pred_lib
+
+
+_risk_lib = None
+
+
+def risk_lib():
+    """The loaded risk-table library (``include/drcvar_loop_risk.h``; raises NativeLibraryError if
+    it is not built: there is no fallback).  It shares the engine library's structs and return
+    codes."""
+    global _risk_lib
+    if _risk_lib is not None:
+        return _risk_lib
+    with _lock:
+        if _risk_lib is None:
+            if not os.path.exists(RISK_LIB_PATH):
+                raise NativeLibraryError(
+                    f"risk-table library not built: {RISK_LIB_PATH} is missing (run "
+                    f"__graft_entry__.build())")
+            try:
+                handle = ctypes.CDLL(RISK_LIB_PATH)
+            except OSError as exc:  # pragma: no cover - depends on the ROCm install
+                raise NativeLibraryError(f"cannot load {RISK_LIB_PATH}: {exc}") from exc
+            i64, i32, dbl, u64, ptr = (ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                                       ctypes.c_uint64, ctypes.c_void_p)
+            handle.drcvar_risk_table_row_bytes.argtypes = []
+            handle.drcvar_risk_table_row_bytes.restype = i64
+            handle.drcvar_risk_table_fill.argtypes = [ptr, ptr, ptr, i64, dbl, dbl, i64, ptr, i64]
+            handle.drcvar_risk_table_fill.restype = ctypes.c_int
+            handle.drcvar_sampled_halfspaces_f64_risk.argtypes = [
+                ptr, i64, i64, i64, i64, i64, i64, i64, i64, dbl, dbl, dbl, u64, ptr, i32,
+                ptr, i64, i64, ptr, i64, ptr, ptr, ptr]
+            handle.drcvar_sampled_halfspaces_f64_risk.restype = ctypes.c_int
+            _risk_lib = handle
+    return _risk_lib
 
 
 def check(code: int) -> None:

@@ -26,14 +26,17 @@
 //
 // samples_out (optional): the kernel also stores the samples it drew; the record is the same bits.
 //
-// Three entries, one kernel template: drcvar_sampled_halfspaces_f64 freezes the stream offset and
+// Four entries, one kernel template: drcvar_sampled_halfspaces_f64 freezes the stream offset and
 // the window in its arguments; drcvar_sampled_halfspaces_f64_dev (DEV below) reads the offset and
 // the window's first path row from a 16-byte state in device memory, so that a receding-horizon
 // loop can be replayed from one graph with a fresh draw per step (simulation/closed_loop.py);
 // drcvar_sampled_halfspaces_f64_pred (PRED below) is the device-state form whose ego is each
-// problem's own predicted path.  The source is compiled twice: into the engine library with the
-// first two entries, and with DRCVAR_LOOP_PRED_LIBRARY into a library of its own
-// (include/drcvar_loop_pred.h) that holds the third and instantiates only the PRED kernels.
+// problem's own predicted path; drcvar_sampled_halfspaces_f64_risk (RISK below) is the device-state
+// form whose risk parameters are each problem's own row of a table in device memory.  The source is
+// compiled three times: into the engine library with the first two entries, with
+// DRCVAR_LOOP_PRED_LIBRARY into a library of its own (include/drcvar_loop_pred.h) that holds the
+// third and instantiates only the PRED kernels, and with DRCVAR_LOOP_RISK_LIBRARY into another
+// (include/drcvar_loop_risk.h) that holds the fourth and instantiates only the RISK kernels.
 //
 // The draw is the sampler's (drcvar_generator.inc) and the selection the stored form's
 // (drcvar_selection.inc); the direction alone differs on purpose, by one more Newton step of the
@@ -48,6 +51,9 @@
 #include "drcvar_sampling.h"
 #ifdef DRCVAR_LOOP_PRED_LIBRARY
 #include "drcvar_loop_pred.h"
+#endif
+#ifdef DRCVAR_LOOP_RISK_LIBRARY
+#include "drcvar_loop_risk.h"
 #endif
 
 namespace {
@@ -88,6 +94,7 @@ __device__ __forceinline__ void store_record(double* rec, double mux, double muy
 //   ISO      the sampler's isotropic LogScale form
 //   DEV      the device-state form (below)
 //   PRED     the device-state form with a predicted ego (below; implies DEV)
+//   RISK     the device-state form with a risk table (below; implies DEV, never with PRED)
 // Blocks of 512 threads are held to 128 VGPRs (four waves per SIMD): two workgroups share a CU,
 // so one unit's draw (VALU) overlaps the other's selection (barriers, LDS, one ranking wave).
 //
@@ -120,6 +127,20 @@ __device__ __forceinline__ void store_record(double* rec, double mux, double muy
 // subtraction differently from the other forms (an ulp of h in 3 units of 24, seen by the bitwise
 // tests).  Measured and not kept: the row as one vector load per wave with
 // readlane in place of the nx scalar loads, 0.322 -> 0.336 ms per launch at B = 1024, N = 20.
+//
+// The risk-table form (RISK, drcvar_sampled_halfspaces_f64_risk): the launch covers B problems of
+// O obstacles each, unit u = (b O + o) T + t, and the unit's Params are row b of `table` in device
+// memory instead of the launch-uniform kernel argument: alpha, delta and epsilon differ from
+// problem to problem inside one launch (the rank of the order statistic, 1 / k, the histogram
+// window and both unbounded exits with them).  A row is what the host would have passed
+// (drcvar_risk_table_fill: make_params with the plan's hist_scale), so per problem the launch is
+// the base form with that row's scalars.  b = (u / T) / O is uniform over the workgroup and every
+// use of prm was already workgroup-uniform, the early return included: the row is a uniform load
+// of a const __restrict__ argument (scalar memory: four s_load of the words the body uses), written
+// before the launch and never by it: the visibility argument is `state`'s.  b < B is the host's check of the unit window
+// against B O T.  The Philox counter is formed from the draw unit ((b mod D) O + o) T + t in place
+// of u: D >= B is DEV's numbering, D = 1 gives every problem the draws of problem 0, and B = S D
+// settings-major gives S settings the same D replicate draws (common random numbers).
 // ---------------------------------------------------------------------------------------------
 constexpr int kMaxStates = 8;  // DRCVAR_MPC_MAX_STATES
 struct NoState {};
@@ -136,15 +157,28 @@ struct PredState {
   int nx, shift;
   double cx[kMaxStates], cy[kMaxStates];  // c_out's two rows, zero past nx
 };
+struct alignas(16) RiskRow {  // one row of the risk table: Params padded to a multiple of 16 bytes
+  Params p;
+};
+struct RiskState {
+  const drcvar_step_state* __restrict__ state;
+  int64_t path_last;
+  const RiskRow* __restrict__ table;  // [B]
+  int64_t O, D;                       // obstacles per problem; the draw period
+};
 
-template <int BLOCK, int PP, int LOG_NB, bool ISO, bool DEV = false, bool PRED = false>
+template <int BLOCK, int PP, int LOG_NB, bool ISO, bool DEV = false, bool PRED = false,
+          bool RISK = false>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BLOCK >= 512 ? 4 : 1)))
 sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __restrict__ ego,
                          DrawArgs a, Params prm, double* __restrict__ out,
                          int32_t* __restrict__ status, double* __restrict__ samples_out,
-                         std::conditional_t<PRED, PredState,
-                                            std::conditional_t<DEV, DevState, NoState>> dev) {
+                         std::conditional_t<
+                             RISK, RiskState,
+                             std::conditional_t<PRED, PredState,
+                                                std::conditional_t<DEV, DevState, NoState>>> dev) {
   static_assert(DEV || !PRED, "the predicted-ego form is a device-state form");
+  static_assert((DEV && !PRED) || !RISK, "the risk-table form is a device-state form without PRED");
   constexpr int NW = BLOCK / kWave;
   constexpr int NB = 1 << LOG_NB;
   constexpr int Q = 2 * PP;  // sample slots per thread: 2 j the pair's first, 2 j + 1 its second
@@ -164,6 +198,12 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
   const int64_t row = blockIdx.x;                              // the unit's row of out / status
   const int64_t u = a.u0 + row;
   const int64_t o = u / a.T, t = u - o * a.T;
+  int64_t ud = u;  // the unit whose Philox counters are drawn
+  if constexpr (RISK) {
+    const int64_t b = o / dev.O;
+    prm = dev.table[b].p;
+    ud = ((b % dev.D) * dev.O + (o - b * dev.O)) * a.T + t;
+  }
   int64_t r = t;  // the unit's row of nominal[o] and of ego
   if constexpr (DEV) {
     const uint64_t words = dev.state->stream_offset;
@@ -214,7 +254,7 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
   // ---- 1. draw -----------------------------------------------------------------------------
   double x[Q], y[Q];
   uint32_t vmask = 0;  // bit q: slot q holds a sample of the unit
-  const uint64_t g0 = static_cast<uint64_t>(u) * static_cast<uint64_t>(pairs) + static_cast<uint64_t>(tid);
+  const uint64_t g0 = static_cast<uint64_t>(ud) * static_cast<uint64_t>(pairs) + static_cast<uint64_t>(tid);
 #pragma unroll
   for (int j = 0; j < PP; ++j) {
     const int p = tid + j * BLOCK;
@@ -411,6 +451,7 @@ struct Launch {
   bool iso;
   hipStream_t stream;
   PredState pred;  // the predicted-ego form's arguments (state and path_last filled at launch)
+  RiskState risk;  // the risk-table form's, likewise
 };
 
 template <int BLOCK, int PP, int LOG_NB, bool ISO>
@@ -423,6 +464,13 @@ void launch_form(const Launch& L) {
   ps.path_last = L.path_last;
   hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true, true>), grid, block, 0,
                      L.stream, L.nominal, nullptr, L.a, L.prm, L.out, L.status, nullptr, ps);
+#elif defined(DRCVAR_LOOP_RISK_LIBRARY)
+  // this library launches the risk-table form alone (L.prm is not read: the rows are the table's)
+  RiskState rs = L.risk;
+  rs.state = L.state;
+  rs.path_last = L.path_last;
+  hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true, false, true>), grid,
+                     block, 0, L.stream, L.nominal, L.ego, L.a, L.prm, L.out, L.status, nullptr, rs);
 #else
   if (L.state)
     hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true>), grid, block, 0,
@@ -447,7 +495,8 @@ void launch_plan(Launch L) {
 // Every entry: the host checks, the launch-uniform arguments and the plan's launch.  `state`
 // non-null selects the device-state form (n_steps is then the window length, path_steps the rows
 // of nominal and ego; stream_offset is unused, the kernel loads it).  `pred` non-null: the
-// predicted-ego form, which has no `ego`.
+// predicted-ego form, which has no `ego`.  `risk` non-null: the risk-table form, whose five risk
+// scalars here are placeholders (its Params are the table's rows).
 int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_steps, int64_t nom_so,
                        int64_t nom_st, int64_t unit_begin, int64_t unit_count, int64_t n_samples,
                        double l00, double l10, double l11, uint64_t seed, uint64_t stream_offset,
@@ -455,7 +504,8 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
                        int32_t zero_first_step, const double* ego, int64_t ego_stride,
                        double robot_radius, double obstacle_radius, double alpha, double delta,
                        double epsilon, double* out, int32_t* status, double* samples_out, int64_t su,
-                       int64_t sn, void* stream, const PredState* pred = nullptr) {
+                       int64_t sn, void* stream, const PredState* pred = nullptr,
+                       const RiskState* risk = nullptr) {
   if (n_obstacles < 0 || n_steps < 0 || n_samples < 0 || unit_begin < 0 || unit_count < 0)
     return DRCVAR_ERR_INVALID_ARGUMENT;
   if (dev && path_steps < 1) return DRCVAR_ERR_INVALID_ARGUMENT;
@@ -507,6 +557,7 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
   L.count = unit_count;
   L.stream = static_cast<hipStream_t>(stream);
   if (pred) L.pred = *pred;
+  if (risk) L.risk = *risk;
   (void)hipGetLastError();  // clear stale errors from unrelated work
   switch (pick_plan(n_samples)) {
     case 0: launch_plan<64, 1, 7>(L); break;
@@ -556,6 +607,59 @@ extern "C" int drcvar_sampled_halfspaces_f64_pred(
                             unit_count, n_samples, l00, l10, l11, seed, 0, state, true, path_steps,
                             zero_first_step, nullptr, 0, robot_radius, obstacle_radius, alpha, delta,
                             epsilon, out, status, nullptr, 0, 0, stream, &ps);
+}
+#elif defined(DRCVAR_LOOP_RISK_LIBRARY)
+static_assert(sizeof(RiskRow) % 16 == 0, "a table row is a multiple of 16 bytes");
+
+extern "C" int64_t drcvar_risk_table_row_bytes(void) { return static_cast<int64_t>(sizeof(RiskRow)); }
+
+extern "C" int drcvar_risk_table_fill(const double* alpha, const double* delta,
+                                      const double* epsilon, int64_t n_problems,
+                                      double robot_radius, double obstacle_radius,
+                                      int64_t n_samples, void* table_host, int64_t table_bytes) {
+  if (n_problems < 0 || table_bytes < 0) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (n_samples < 1 || n_samples > DRCVAR_MAX_SAMPLES) return DRCVAR_ERR_UNSUPPORTED;
+  if (n_problems == 0) return DRCVAR_OK;
+  if (!alpha || !delta || !epsilon || !table_host) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (n_problems > table_bytes / static_cast<int64_t>(sizeof(RiskRow)))
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  for (int64_t b = 0; b < n_problems; ++b)  // every row first: a rejected row writes nothing
+    if (!params_ok(robot_radius, obstacle_radius, alpha[b], delta[b], epsilon[b]))
+      return DRCVAR_ERR_INVALID_ARGUMENT;
+  const double bins = static_cast<double>(1 << kPlans[pick_plan(n_samples)].log_nb);
+  for (int64_t b = 0; b < n_problems; ++b) {
+    RiskRow row;
+    std::memset(&row, 0, sizeof(row));  // the padding too: equal triples give equal bytes
+    row.p = make_params(robot_radius, obstacle_radius, alpha[b], delta[b], epsilon[b], n_samples);
+    row.p.hist_scale = bins / (2.0 * row.p.window_sd);  // as launch_plan sets it
+    std::memcpy(static_cast<char*>(table_host) + b * sizeof(RiskRow), &row, sizeof(row));
+  }
+  return DRCVAR_OK;
+}
+
+extern "C" int drcvar_sampled_halfspaces_f64_risk(
+    const double* nominal_path, int64_t n_obstacles, int64_t path_steps, int64_t nom_so,
+    int64_t nom_st, int64_t n_steps, int64_t unit_begin, int64_t unit_count, int64_t n_samples,
+    double l00, double l10, double l11, uint64_t seed, const drcvar_step_state* state,
+    int32_t zero_first_step, const double* ego_path, int64_t ego_stride,
+    int64_t n_obstacles_per_problem, const void* table, int64_t draw_period, double* out,
+    int32_t* status, void* stream) {
+  if (n_obstacles_per_problem < 1 || draw_period < 1) return DRCVAR_ERR_INVALID_ARGUMENT;
+  // whole problems: b = (u / T) / O must stay below the rows of the table
+  if (n_obstacles > 0 && n_obstacles % n_obstacles_per_problem != 0)
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  const bool launches = unit_count > 0 && n_samples > 0;
+  if (launches && (!table || reinterpret_cast<uintptr_t>(table) % 16 != 0))
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  RiskState rs{};
+  rs.table = static_cast<const RiskRow*>(table);
+  rs.O = n_obstacles_per_problem;
+  rs.D = draw_period;
+  // (placeholder risk scalars that params_ok accepts: the kernel reads the table's rows)
+  return sampled_halfspaces(nominal_path, n_obstacles, n_steps, nom_so, nom_st, unit_begin,
+                            unit_count, n_samples, l00, l10, l11, seed, 0, state, true, path_steps,
+                            zero_first_step, ego_path, ego_stride, 0.0, 0.0, 1.0, 0.0, 0.0, out,
+                            status, nullptr, 0, 0, stream, nullptr, &rs);
 }
 #else
 extern "C" int drcvar_sampled_launch_plan(int64_t n_samples, int32_t* threads,

@@ -15,6 +15,9 @@ These are the batched calls everything else is built on:
   loop replayed from one graph (``simulation/closed_loop.py``).
 * :func:`sampled_halfspaces_pred` — ``drcvar_sampled_halfspaces_f64_pred``: that launch for a
   batch of loops, each unit's ego taken from its own problem's state and predicted path.
+* :func:`sampled_halfspaces_risk` — ``drcvar_sampled_halfspaces_f64_risk``: that launch for a
+  batch of loops, each unit's risk parameters taken from its own problem's row of a
+  :class:`RiskTable`, the draws shared between problems by a draw period.
 
 All enqueue one kernel on the current HIP stream and return without synchronising.  Inputs must
 be float64 CUDA tensors whose two coordinates are adjacent (last stride 1); any other strides are
@@ -488,6 +491,166 @@ def sampled_halfspaces_pred(nominal_path: torch.Tensor, x0: torch.Tensor, pred: 
     each problem's about its own state and predicted path."""
     launch, out = prepare_sampled_halfspaces_pred(nominal_path, x0, pred, c_out, n_obstacles,
                                                   n_steps, n_samples, params, state, **kwargs)
+    if out.numel() > 0:
+        launch()
+    return out
+
+
+@dataclass(frozen=True)
+class RiskTable:
+    """Risk parameters per problem of a batch (``include/drcvar_loop_risk.h``): ``alpha``,
+    ``delta`` and ``epsilon`` are each a scalar or a sequence of one length B, broadcast to B
+    (B = 1 when all three are scalars); the radii are scalars."""
+
+    alpha: object = 0.2
+    delta: object = 0.1
+    epsilon: object = 0.15
+    robot_radius: float = 0.3
+    obstacle_radius: float = 0.3
+
+    def _columns(self):
+        """(alpha, delta, epsilon) as float64 arrays ``[B]``."""
+        import numpy as np
+        cols = [np.asarray(v, dtype=np.float64) for v in (self.alpha, self.delta, self.epsilon)]
+        if any(c.ndim > 1 for c in cols):
+            raise ValueError("alpha, delta and epsilon must be scalars or one-dimensional")
+        lengths = {c.shape[0] for c in cols if c.ndim == 1}
+        if len(lengths) > 1:
+            raise ValueError(f"alpha, delta and epsilon have different lengths {sorted(lengths)}")
+        B = lengths.pop() if lengths else 1
+        return tuple(np.ascontiguousarray(np.broadcast_to(c, (B,))) for c in cols)
+
+    def __len__(self) -> int:
+        return int(self._columns()[0].shape[0])
+
+    def validate(self) -> None:
+        alpha, delta, epsilon = self._columns()
+        if alpha.shape[0] < 1:
+            raise ValueError("a risk table needs at least one row")
+        radii = (float(self.robot_radius), float(self.obstacle_radius))
+        if not all(math.isfinite(v) for v in (*radii, *alpha, *delta, *epsilon)):
+            raise ValueError(f"risk parameters must be finite: {self}")
+        if not (alpha > 0.0).all():
+            raise ValueError(f"alpha must be > 0 in every row, got {alpha.tolist()}")
+
+    def row(self, b: int) -> RiskParams:
+        """Problem ``b``'s parameters as the launch-uniform entries take them."""
+        alpha, delta, epsilon = self._columns()
+        return RiskParams(float(self.robot_radius), float(self.obstacle_radius), float(alpha[b]),
+                          float(delta[b]), float(epsilon[b]))
+
+    def to_device(self, n_samples: int, device) -> torch.Tensor:
+        """The filled table for ``n_samples`` as a uint8 tensor ``[B, row_bytes]`` on ``device``
+        (``drcvar_risk_table_fill`` into host memory, one copy): a table belongs to one
+        ``n_samples``."""
+        import numpy as np
+        self.validate()
+        alpha, delta, epsilon = self._columns()
+        B = alpha.shape[0]
+        lib = _native.risk_lib()
+        row = int(lib.drcvar_risk_table_row_bytes())
+        host = np.zeros((B, row), dtype=np.uint8)
+        _native.check(lib.drcvar_risk_table_fill(
+            alpha.ctypes.data, delta.ctypes.data, epsilon.ctypes.data, B, float(self.robot_radius),
+            float(self.obstacle_radius), int(n_samples), host.ctypes.data, host.nbytes))
+        return torch.from_numpy(host).to(device)
+
+
+def prepare_sampled_halfspaces_risk(nominal_path: torch.Tensor, ego_path: torch.Tensor,
+                                    n_obstacles: int, n_steps: int, n_samples: int,
+                                    params: RiskTable, state: torch.Tensor, *,
+                                    draw_period: int | None = None, table: torch.Tensor | None = None,
+                                    noise_cov=DEFAULT_NOISE_COV, seed: int = 0,
+                                    zero_first_step: bool = True, unit_begin: int = 0,
+                                    unit_count: int | None = None, out: torch.Tensor | None = None,
+                                    status: torch.Tensor | None = None, stream=None,
+                                    chol=None) -> tuple[PreparedLaunch, torch.Tensor]:
+    """Freeze one ``drcvar_sampled_halfspaces_f64_risk`` call (``include/drcvar_loop_risk.h``):
+    :func:`prepare_sampled_halfspaces_dev` for B problems of ``n_obstacles`` = O obstacles each,
+    with the risk parameters of every unit taken from its own problem's row of ``params`` (a
+    :class:`RiskTable` of B rows) and draws shared between problems by ``draw_period``.
+
+    nominal_path ``[B O, P, 2]`` (problem b's obstacles are rows ``b O .. b O + O - 1``) and
+    ego_path ``[P, 2]`` as in :func:`prepare_sampled_halfspaces_dev`.  Unit ``u = (b O + o) T + t``
+    takes what that entry's unit takes, but filters with ``params.row(b)`` and draws the Philox
+    counters of unit ``((b mod D) O + o) T + t``, ``D = draw_period`` (None: B, the entry's own
+    draws; 1: every problem meets problem 0's draws; B = S D with ``b = s D + r``: S settings on
+    the same D replicate draws).  Per problem the records and status words are bit for bit those of
+    :func:`sampled_halfspaces` on a nominal tensor whose rows ``(b mod D) O .. + O`` are the
+    problem's gathered window, with the gathered ego window, ``unit_begin = (b mod D) O T``,
+    ``unit_count = O T``, the state's offset and ``params.row(b)``.
+
+    ``table`` (optional): ``params.to_device(n_samples, device)`` made earlier, so that several
+    launches share one copy; the entry cannot check device memory, so the table is only accepted
+    with the shape that ``params`` and the library give it.  ``out`` is ``[B O, n_steps, 8]``, or
+    ``[unit_count, 8]`` for a unit window; ``status``, ``stream`` and ``chol`` as in
+    :func:`prepare_sampled_halfspaces_dev`."""
+    if not isinstance(params, RiskTable):
+        raise ValueError("params must be a RiskTable")
+    params.validate()
+    if not isinstance(nominal_path, torch.Tensor) or nominal_path.dim() != 3 or nominal_path.shape[0] < 1:
+        raise ValueError("nominal_path must be float64 [B O, P, 2] with B O, P >= 1")
+    check_path(nominal_path, "nominal_path", (None, None, 2))
+    dev = nominal_path.device
+    BO, P, _ = nominal_path.shape
+    O = int(n_obstacles)
+    if O < 1 or BO % O != 0:
+        raise ValueError(f"n_obstacles={O} must be at least 1 and divide nominal_path's {BO} rows")
+    B = BO // O
+    if len(params) != B:
+        raise ValueError(f"the risk table has {len(params)} rows, the launch {B} problems")
+    D = B if draw_period is None else int(draw_period)
+    if D < 1:
+        raise ValueError(f"draw_period={draw_period} must be at least 1")
+    check_path(ego_path, "ego_path", (P, 2), dev)
+    check_step_state(state, dev)
+    T, n = int(n_steps), int(n_samples)
+    if T < 0:
+        raise ValueError(f"n_steps={T} must not be negative")
+    if n < 1 or n > _native.MAX_SAMPLES:
+        raise ValueError(f"n_samples={n} outside 1..{_native.MAX_SAMPLES}")
+    whole = unit_count is None
+    u0 = int(unit_begin)
+    count = BO * T - u0 if whole else int(unit_count)
+    if u0 < 0 or count < 0 or u0 + count > BO * T:
+        raise ValueError(f"unit range [{u0}, {u0 + count}) outside the {BO} x {T} grid")
+    whole = whole and u0 == 0
+    shape = (BO, T, OUT_WIDTH) if whole else (count, OUT_WIDTH)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=dev)
+    else:
+        _check_out(out, shape, dev, "[B O, T, 8]" if whole else "[units, 8]")
+    if status is not None:
+        _check_status(status, count, dev)
+    if table is None:
+        table = params.to_device(n, dev)
+    row = int(_native.risk_lib().drcvar_risk_table_row_bytes())
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or table.device != dev or \
+            tuple(table.shape) != (B, row) or not table.is_contiguous() or table.data_ptr() % 16 != 0:
+        raise ValueError(f"table must be a contiguous, 16-byte aligned uint8 [{B}, {row}] tensor on "
+                         f"{dev} (RiskTable.to_device)")
+    l00, l10, l11 = _noise_factor(noise_cov, chol)
+    args = (ctypes.c_void_p(nominal_path.data_ptr()), BO, P, nominal_path.stride(0),
+            nominal_path.stride(1), T, u0, count, n, l00, l10, l11,
+            ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), ctypes.c_void_p(state.data_ptr()),
+            ctypes.c_int32(1 if zero_first_step else 0),
+            ctypes.c_void_p(ego_path.data_ptr()), ego_path.stride(0), O,
+            ctypes.c_void_p(table.data_ptr()), D, ctypes.c_void_p(out.data_ptr()),
+            ctypes.c_void_p(status.data_ptr() if status is not None else None),
+            ctypes.c_void_p(_stream_handle(dev, stream)))
+    launch = PreparedLaunch(_native.risk_lib().drcvar_sampled_halfspaces_f64_risk, args,
+                            (nominal_path, ego_path, state, table, out, status))
+    return launch, out
+
+
+def sampled_halfspaces_risk(nominal_path: torch.Tensor, ego_path: torch.Tensor, n_obstacles: int,
+                            n_steps: int, n_samples: int, params: RiskTable, state: torch.Tensor,
+                            **kwargs) -> torch.Tensor:
+    """One ``drcvar_sampled_halfspaces_f64_risk`` launch (arguments:
+    :func:`prepare_sampled_halfspaces_risk`): the halfspaces of the window that ``state`` names,
+    each problem's with its own risk parameters."""
+    launch, out = prepare_sampled_halfspaces_risk(nominal_path, ego_path, n_obstacles, n_steps,
+                                                  n_samples, params, state, **kwargs)
     if out.numel() > 0:
         launch()
     return out

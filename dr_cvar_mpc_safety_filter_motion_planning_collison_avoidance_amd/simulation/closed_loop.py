@@ -36,6 +36,12 @@ Both classes take ``evaluate=LoopEvaluation(...)``: a fourth launch per control 
 against M noise realisations of the obstacles and keeps the running minimum clearance and the
 per-step collision counts on the device; ``safety()`` returns them.  With
 ``evaluate=None`` a step is the three launches above and nothing else changes.
+
+:class:`RecedingHorizonBatch` also takes ``params=engine.RiskTable(...)``: every loop then filters
+with its OWN (alpha, delta, epsilon), launch 1 being ``drcvar_sampled_halfspaces_f64_risk``
+(``include/drcvar_loop_risk.h``), and ``draw_period=D`` gives problems ``b`` and
+``b + D`` the same draws, so a grid of settings x D replicates is one batch on common random
+numbers.  With a ``RiskParams`` nothing changes.
 """
 from __future__ import annotations
 
@@ -285,6 +291,30 @@ def check_linearize(linearize, relinearize):
         raise ValueError('relinearize > 0 needs linearize="predicted"')
 
 
+def check_risk(params, draw_period, n_problems, linearize):
+    """The ``params=`` / ``draw_period=`` arguments of the loop classes (host only).  Returns the
+    draw period of a :class:`engine.RiskTable` (``None`` = ``n_problems``), and None for a
+    ``RiskParams``; ``n_problems=None`` is the single-loop class, which takes no table."""
+    if not isinstance(params, engine.RiskTable):
+        if draw_period is not None:
+            raise ValueError("draw_period needs params=RiskTable(...): a RiskParams batch draws "
+                             "every problem's own units")
+        return None
+    if n_problems is None:
+        raise ValueError("a RiskTable belongs to RecedingHorizonBatch; RecedingHorizonFilter takes "
+                         "a RiskParams")
+    if linearize == "predicted":
+        raise ValueError('a RiskTable cannot be combined with linearize="predicted"')
+    params.validate()
+    if len(params) != int(n_problems):
+        raise ValueError(f"the RiskTable has {len(params)} rows, n_problems={n_problems}")
+    if draw_period is None:
+        return int(n_problems)
+    if isinstance(draw_period, bool) or int(draw_period) != draw_period or int(draw_period) < 1:
+        raise ValueError(f"draw_period={draw_period!r} must be a positive integer or None")
+    return int(draw_period)
+
+
 class _Linearized:
     """What the two loop classes share for ``linearize="predicted"``: the
     halfspaces of window row t are taken about the loop's own prediction for that path time
@@ -374,6 +404,7 @@ class RecedingHorizonFilter(_Evaluated, _Linearized):
             raise ValueError(f"steps_per_graph={steps_per_graph} must be at least 1")
         check_evaluate(evaluate)
         check_linearize(linearize, relinearize)
+        check_risk(params, None, None, linearize)   # (a RiskTable is the batch class's)
         n = int(n_samples)
         if n < 1 or n > _native.MAX_SAMPLES:
             raise ValueError(f"n_samples={n} outside 1..{_native.MAX_SAMPLES}")
@@ -681,6 +712,17 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
     loop's own motion and therefore its metric; the DRAWS are still common random numbers across
     batches with the same seed and offset.
 
+    ``params=engine.RiskTable(...)`` (B rows) gives every loop its own (alpha, delta, epsilon):
+    step 1 is then one ``drcvar_sampled_halfspaces_f64_risk`` launch (``include/drcvar_loop_risk.h``,
+    DESIGN.md §5.7) whose unit reads its problem's row of the table, and ``draw_period=D`` (None:
+    B) makes problem b draw unit ``((b mod D) O + o) H + t``: with B = S D and ``b = s D + r``, S
+    settings meet the same D replicate draws in one batch (common random numbers), D = 1 gives every
+    problem the same draws.  The solve, the advance and the evaluation launch are untouched, the
+    radii stay scalars (``LoopEvaluation`` has scalar radii), and the ``reference`` backend calls
+    ``engine.sampled_halfspaces`` per problem with ``params.row(b)``.  A ``RiskTable`` with
+    ``linearize="predicted"``, one whose length is not B, or a ``draw_period`` beside a
+    ``RiskParams`` is a ``ValueError``; with a ``RiskParams`` the batch is what it was.
+
     ``reset(x0)`` takes ``[B, nx]`` or ``[nx]``.  ``run(n, backend)`` returns ``(states [B, n + 1,
     nx], inputs [B, n, nu], info [B, n, 10])``; backends, log capacity, rebasing, the limit of D
     steps per reset under a disturbance and the treatment of failed solves (a logged step; nothing
@@ -693,13 +735,14 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
                  n_problems, metric="dr_cvar", noise_cov=DEFAULT_NOISE_COV, chol=None, seed=0,
                  zero_first_step=True, max_iter=DEFAULT_MAX_ITER, tol=DEFAULT_TOL, polish=True,
                  options=None, disturbance=None, steps_per_graph=1, evaluate=None,
-                 linearize="reference", relinearize=0):
+                 linearize="reference", relinearize=0, draw_period=None):
         if metric not in METRIC_COLUMNS:
             raise ValueError(f"metric must be one of {tuple(METRIC_COLUMNS)}, got {metric!r}")
         if int(steps_per_graph) < 1:
             raise ValueError(f"steps_per_graph={steps_per_graph} must be at least 1")
         check_evaluate(evaluate)
         check_linearize(linearize, relinearize)
+        self.draw_period = check_risk(params, draw_period, n_problems, linearize)
         n = int(n_samples)
         if n < 1 or n > _native.MAX_SAMPLES:
             raise ValueError(f"n_samples={n} outside 1..{_native.MAX_SAMPLES}")
@@ -743,6 +786,8 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         self._rows = {k: torch.arange(k, device=dev) for k in (H, H + 1)}
         self._eval_init(evaluate, B, O, self.nominal_path)
         self._lin_init(linearize, relinearize, B, O, self.nominal_path)
+        # a RiskTable: filled for n_samples and copied to the device once
+        self._risk_table = params.to_device(n, dev) if self.draw_period is not None else None
         self._logs = None           # (x_log [B, cap + 1, nx], u_log [B, cap, nu], info_log [B, cap, 10])
         self._cap, self._step_begin = 0, 0
         self._primed = False
@@ -815,6 +860,12 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         if self.linearize == "predicted":
             halfspaces = self._lin_launch(stream, 1)
             again = self._lin_launch(stream, 0) if self.relinearize else None
+        elif self._risk_table is not None:
+            halfspaces, _ = engine.prepare_sampled_halfspaces_risk(
+                self.nominal_path, self.ego_path, self.n_obstacles, H, self.n_samples, self.params,
+                self._state[0], draw_period=self.draw_period, table=self._risk_table,
+                noise_cov=self.noise_cov, seed=self.seed, zero_first_step=self.zero_first_step,
+                out=self._record, stream=stream, chol=self.chol)
         else:
             halfspaces, _ = engine.prepare_sampled_halfspaces_dev(
                 self.nominal_path, self.ego_path, H, self.n_samples, self.params, self._state[0],
@@ -863,6 +914,23 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
                 *self._logs, *evaluated, *predicted]
 
     # ---- the semantics, from the entry points that predate the loop -----------------------------
+    def _risk_reference_record(self, window, ego_window):
+        """The record ``[B O, H, 8]`` of a RiskTable batch from the entry that predates the table:
+        per problem one ``engine.sampled_halfspaces`` call with ``params.row(b)`` on a nominal
+        tensor whose obstacle rows ``(b mod D) O .. + O`` are the problem's gathered window (the
+        rows before them are never read) and the unit window that starts there."""
+        H, B, O, D = self.model.horizon, self.n_problems, self.n_obstacles, self.draw_period
+        records = []
+        for b in range(B):
+            r = b % D
+            nominal = torch.zeros(((r + 1) * O, H, 2), dtype=torch.float64, device=window.device)
+            nominal[r * O:].copy_(window[b * O:(b + 1) * O])
+            records.append(engine.sampled_halfspaces(
+                nominal, ego_window, self.n_samples, self.params.row(b), noise_cov=self.noise_cov,
+                chol=self.chol, seed=self.seed, stream_offset=self._offset,
+                zero_first_step=self.zero_first_step, unit_begin=r * O * H, unit_count=O * H))
+        return torch.cat(records).view(B * O, H, engine.OUT_WIDTH)
+
     def _reference_step(self, i):
         m = self.model
         H, B = m.horizon, self.n_problems
@@ -872,6 +940,8 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         for p in range(1 + self.relinearize):
             if self.linearize == "predicted":
                 record = self._lin_reference_record(window, 1 if p == 0 else 0)
+            elif self._risk_table is not None:
+                record = self._risk_reference_record(window, self._window(self.ego_path, s, H))
             else:
                 ego_window = self._window(self.ego_path, s, H)
                 record = engine.sampled_halfspaces(window, ego_window, self.n_samples, self.params,
