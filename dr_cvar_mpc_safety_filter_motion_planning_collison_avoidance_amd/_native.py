@@ -2,8 +2,9 @@
 ``include/drcvar_halfspace.h`` (+ ``drcvar_mpc.h``, ``drcvar_sampling.h``, ``drcvar_exchange.h``)
 bound with ctypes; beside it the loop library (``drcvar_loop.h``, :func:`loop_lib`), the
 loop-evaluation library (``drcvar_loop_eval.h``, :func:`eval_lib`), the predicted-ego library
-(``drcvar_loop_pred.h``, :func:`pred_lib`) and the risk-table library (``drcvar_loop_risk.h``,
-:func:`risk_lib`), one entry family each.
+(``drcvar_loop_pred.h``, :func:`pred_lib`), the risk-table library (``drcvar_loop_risk.h``,
+:func:`risk_lib`) and the metric library (``drcvar_loop_metric.h``, :func:`metric_lib`), one entry
+family each.
 
 There is deliberately no fallback: if the shared library is missing or cannot be loaded every
 entry point raises :class:`NativeLibraryError`.  ``build()`` compiles it for gfx950 in-tree.
@@ -57,6 +58,13 @@ RISK_HEADER = os.path.join(INCLUDE_DIR, "drcvar_loop_risk.h")
 RISK_UNIT = (os.path.join(PKG_DIR, "csrc", "drcvar_sampled.hip"), ("-DDRCVAR_LOOP_RISK_LIBRARY",))
 RISK_SYMBOLS = ("drcvar_risk_table_row_bytes", "drcvar_risk_table_fill",
                 "drcvar_sampled_halfspaces_f64_risk")
+# The metric library (include/drcvar_loop_metric.h), by the same recipe: csrc/drcvar_sampled.hip
+# compiled a fourth time, with DRCVAR_LOOP_METRIC_LIBRARY (14 kernels: the seven plans x ISO of the
+# metric form, none of the other three libraries').
+METRIC_LIB_PATH = os.path.join(LIB_DIR, "libdrcvar_loop_metric.so")
+METRIC_HEADER = os.path.join(INCLUDE_DIR, "drcvar_loop_metric.h")
+METRIC_UNIT = (os.path.join(PKG_DIR, "csrc", "drcvar_sampled.hip"), ("-DDRCVAR_LOOP_METRIC_LIBRARY",))
+METRIC_SYMBOLS = ("drcvar_metric_table_row_bytes", "drcvar_sampled_halfspaces_f64_metric")
 
 ABI_VERSION = 3
 OUT_WIDTH = 8
@@ -283,11 +291,12 @@ def build(verbose: bool = False, extra_flags=()) -> str:
     os.makedirs(obj_dir, exist_ok=True)
     import glob
     incs = sorted(glob.glob(os.path.join(PKG_DIR, "csrc", "*.inc")))  # tables the sources include
-    headers = b"".join(open(h, "rb").read() for h in HEADERS + [LOOP_HEADER, EVAL_HEADER, PRED_HEADER, RISK_HEADER] + incs)
+    headers = b"".join(open(h, "rb").read() for h in HEADERS + [LOOP_HEADER, EVAL_HEADER, PRED_HEADER, RISK_HEADER,
+                                                                   METRIC_HEADER] + incs)
     # the compiler's identity is part of every key: objects of an older hipcc / ROCm are rebuilt
     toolchain = _toolchain(probe=True)
     objs, procs = [], []
-    for src, defs in _compile_units() + [LOOP_UNIT, EVAL_UNIT, PRED_UNIT, RISK_UNIT]:
+    for src, defs in _compile_units() + [LOOP_UNIT, EVAL_UNIT, PRED_UNIT, RISK_UNIT, METRIC_UNIT]:
         flags = _unit_flags(defs, extra_flags)
         key = hashlib.sha256(open(src, "rb").read() + headers + toolchain
                              + " ".join(flags).encode()).hexdigest()[:16]
@@ -305,11 +314,11 @@ def build(verbose: bool = False, extra_flags=()) -> str:
         raise subprocess.CalledProcessError(1, failed[0])
     for _, obj, _ in procs:
         os.replace(obj + ".tmp", obj)
-    # (LOOP_UNIT, EVAL_UNIT, PRED_UNIT and RISK_UNIT are the last four: each is a library of its
-    # own)
-    for path, members in ((LIB_PATH, objs[:-4]), (LOOP_LIB_PATH, objs[-4:-3]),
-                          (EVAL_LIB_PATH, objs[-3:-2]), (PRED_LIB_PATH, objs[-2:-1]),
-                          (RISK_LIB_PATH, objs[-1:])):
+    # (LOOP_UNIT, EVAL_UNIT, PRED_UNIT, RISK_UNIT and METRIC_UNIT are the last five: each is a
+    # library of its own)
+    for path, members in ((LIB_PATH, objs[:-5]), (LOOP_LIB_PATH, objs[-5:-4]),
+                          (EVAL_LIB_PATH, objs[-4:-3]), (PRED_LIB_PATH, objs[-3:-2]),
+                          (RISK_LIB_PATH, objs[-2:-1]), (METRIC_LIB_PATH, objs[-1:])):
         link = ["hipcc", f"--offload-arch={OFFLOAD_ARCH}", "-shared", "-fPIC", *members,
                 "-o", path + ".tmp"]
         if verbose:
@@ -563,6 +572,46 @@ def risk_lib():
             handle.drcvar_sampled_halfspaces_f64_risk.restype = ctypes.c_int
             _risk_lib = handle
     return _risk_lib
+
+
+_metric_lib = None
+
+
+def metric_lib():
+    """The loaded metric library (``include/drcvar_loop_metric.h``; raises NativeLibraryError if it
+    is not built: there is no fallback).  It shares the engine library's structs and return codes,
+    and reads the rows the risk-table library fills: the two row sizes are checked equal here,
+    once."""
+    global _metric_lib
+    if _metric_lib is not None:
+        return _metric_lib
+    risk = risk_lib()
+    with _lock:
+        if _metric_lib is None:
+            if not os.path.exists(METRIC_LIB_PATH):
+                raise NativeLibraryError(
+                    f"metric library not built: {METRIC_LIB_PATH} is missing (run "
+                    f"__graft_entry__.build())")
+            try:
+                handle = ctypes.CDLL(METRIC_LIB_PATH)
+            except OSError as exc:  # pragma: no cover - depends on the ROCm install
+                raise NativeLibraryError(f"cannot load {METRIC_LIB_PATH}: {exc}") from exc
+            i64, i32, dbl, u64, ptr = (ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                                       ctypes.c_uint64, ctypes.c_void_p)
+            handle.drcvar_metric_table_row_bytes.argtypes = []
+            handle.drcvar_metric_table_row_bytes.restype = i64
+            handle.drcvar_sampled_halfspaces_f64_metric.argtypes = [
+                ptr, i64, i64, i64, i64, i64, i64, i64, i64, dbl, dbl, dbl, u64, ptr, i32,
+                ptr, i64, i64, ptr, i64, ptr, ptr, ptr, ptr, ptr]
+            handle.drcvar_sampled_halfspaces_f64_metric.restype = ctypes.c_int
+            rows = (int(handle.drcvar_metric_table_row_bytes()),
+                    int(risk.drcvar_risk_table_row_bytes()))
+            if rows[0] != rows[1]:
+                raise NativeLibraryError(
+                    f"{METRIC_LIB_PATH} reads table rows of {rows[0]} bytes, {RISK_LIB_PATH} fills "
+                    f"rows of {rows[1]}: the two libraries are not of one build")
+            _metric_lib = handle
+    return _metric_lib
 
 
 def check(code: int) -> None:

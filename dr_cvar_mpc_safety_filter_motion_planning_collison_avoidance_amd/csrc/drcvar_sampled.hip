@@ -26,17 +26,20 @@
 //
 // samples_out (optional): the kernel also stores the samples it drew; the record is the same bits.
 //
-// Four entries, one kernel template: drcvar_sampled_halfspaces_f64 freezes the stream offset and
+// Five entries, one kernel template: drcvar_sampled_halfspaces_f64 freezes the stream offset and
 // the window in its arguments; drcvar_sampled_halfspaces_f64_dev (DEV below) reads the offset and
 // the window's first path row from a 16-byte state in device memory, so that a receding-horizon
 // loop can be replayed from one graph with a fresh draw per step (simulation/closed_loop.py);
 // drcvar_sampled_halfspaces_f64_pred (PRED below) is the device-state form whose ego is each
 // problem's own predicted path; drcvar_sampled_halfspaces_f64_risk (RISK below) is the device-state
-// form whose risk parameters are each problem's own row of a table in device memory.  The source is
-// compiled three times: into the engine library with the first two entries, with
-// DRCVAR_LOOP_PRED_LIBRARY into a library of its own (include/drcvar_loop_pred.h) that holds the
-// third and instantiates only the PRED kernels, and with DRCVAR_LOOP_RISK_LIBRARY into another
-// (include/drcvar_loop_risk.h) that holds the fourth and instantiates only the RISK kernels.
+// form whose risk parameters are each problem's own row of a table in device memory;
+// drcvar_sampled_halfspaces_f64_metric (METRIC below) is the risk-table form that also stores each
+// unit's halfspace under its problem's own metric.  The source is compiled four times: into the
+// engine library with the first two entries, with DRCVAR_LOOP_PRED_LIBRARY into a library of its
+// own (include/drcvar_loop_pred.h) that holds the third and instantiates only the PRED kernels,
+// with DRCVAR_LOOP_RISK_LIBRARY into another (include/drcvar_loop_risk.h) that holds the fourth and
+// instantiates only the RISK kernels, and with DRCVAR_LOOP_METRIC_LIBRARY into a last one
+// (include/drcvar_loop_metric.h) that holds the fifth and instantiates only the METRIC kernels.
 //
 // The draw is the sampler's (drcvar_generator.inc) and the selection the stored form's
 // (drcvar_selection.inc); the direction alone differs on purpose, by one more Newton step of the
@@ -55,6 +58,7 @@
 #ifdef DRCVAR_LOOP_RISK_LIBRARY
 #include "drcvar_loop_risk.h"
 #endif
+#include "drcvar_loop_metric.h"  // every build: the METRIC form's constants (no code without it)
 
 namespace {
 
@@ -71,19 +75,42 @@ struct DrawArgs {
   LogScale lg;
 };
 
-// The whole record by one lane, plain stores.
-__device__ __forceinline__ void store_record(double* rec, double mux, double muy, double rc,
-                                             double h0, double h1, const Offsets& g) {
-  double m0, m1, gm;
-  mean_halfspace(mux, muy, rc, &m0, &m1, &gm);
-  rec[DRCVAR_COL_MEAN_H0] = m0;
-  rec[DRCVAR_COL_MEAN_H1] = m1;
-  rec[DRCVAR_COL_G_MEAN] = gm;
+// The whole record by one lane, plain stores; hands back the mean halfspace it stored.
+__device__ __forceinline__ void store_record_mean(double* rec, double mux, double muy, double rc,
+                                                  double h0, double h1, const Offsets& g,
+                                                  double* m0, double* m1, double* gm) {
+  mean_halfspace(mux, muy, rc, m0, m1, gm);
+  rec[DRCVAR_COL_MEAN_H0] = *m0;
+  rec[DRCVAR_COL_MEAN_H1] = *m1;
+  rec[DRCVAR_COL_G_MEAN] = *gm;
   rec[DRCVAR_COL_H0] = h0;
   rec[DRCVAR_COL_H1] = h1;
   rec[DRCVAR_COL_G_CVAR] = g.g_cvar;
   rec[DRCVAR_COL_G_DR_STAR] = g.g_star;
   rec[DRCVAR_COL_G_DR_TILDE] = g.g_tilde;
+}
+
+__device__ __forceinline__ void store_record(double* rec, double mux, double muy, double rc,
+                                             double h0, double h1, const Offsets& g) {
+  double m0, m1, gm;
+  store_record_mean(rec, mux, muy, rc, h0, h1, g, &m0, &m1, &gm);
+}
+
+// store_record, and by the same lane the unit's halfspace under metric `code` from the values it
+// has just stored (core/mpc_filter.METRIC_COLUMNS): sel = (h0, h1, g, +0.0), three quiet NaNs for
+// any other code.  Nothing is indexed by the code.
+__device__ __forceinline__ void store_record_selected(double* rec, double* sel, int32_t code,
+                                                      double mux, double muy, double rc, double h0,
+                                                      double h1, const Offsets& g) {
+  double m0, m1, gm;
+  store_record_mean(rec, mux, muy, rc, h0, h1, g, &m0, &m1, &gm);
+  const bool mean = code == DRCVAR_METRIC_MEAN;
+  const bool known = mean || code == DRCVAR_METRIC_CVAR || code == DRCVAR_METRIC_DR_CVAR;
+  const double nan = __builtin_nan("");
+  sel[DRCVAR_SEL_H0] = known ? (mean ? m0 : h0) : nan;
+  sel[DRCVAR_SEL_H1] = known ? (mean ? m1 : h1) : nan;
+  sel[DRCVAR_SEL_G] = known ? (mean ? gm : (code == DRCVAR_METRIC_CVAR ? g.g_cvar : g.g_tilde)) : nan;
+  sel[DRCVAR_SEL_WIDTH - 1] = 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -95,6 +122,7 @@ __device__ __forceinline__ void store_record(double* rec, double mux, double muy
 //   DEV      the device-state form (below)
 //   PRED     the device-state form with a predicted ego (below; implies DEV)
 //   RISK     the device-state form with a risk table (below; implies DEV, never with PRED)
+//   METRIC   the risk-table form with a metric per problem (below; implies RISK)
 // Blocks of 512 threads are held to 128 VGPRs (four waves per SIMD): two workgroups share a CU,
 // so one unit's draw (VALU) overlaps the other's selection (barriers, LDS, one ranking wave).
 //
@@ -141,6 +169,15 @@ __device__ __forceinline__ void store_record(double* rec, double mux, double muy
 // against B O T.  The Philox counter is formed from the draw unit ((b mod D) O + o) T + t in place
 // of u: D >= B is DEV's numbering, D = 1 gives every problem the draws of problem 0, and B = S D
 // settings-major gives S settings the same D replicate draws (common random numbers).
+//
+// The metric form (METRIC, drcvar_sampled_halfspaces_f64_metric): the risk-table form, whose lane
+// that stores the unit's record also stores selected[row] = (h0, h1, g, +0.0), the halfspace under
+// metric[b] (0 mean, 1 CVaR, 2 DR-CVaR; any other code: three quiet NaNs), from the values it holds
+// for the record: no launch and no pass over the record is added for a batch whose problems filter
+// under different metrics.  out and status are the RISK form's bytes.  metric[b] is one more
+// uniform load of a const __restrict__ argument beside the table row, before barrier 0, written
+// before the launch and never by it (`state`'s visibility argument); both storing exits (the
+// bad / unbounded return and the finish, which the noise-free step reaches too) store the row.
 // ---------------------------------------------------------------------------------------------
 constexpr int kMaxStates = 8;  // DRCVAR_MPC_MAX_STATES
 struct NoState {};
@@ -166,19 +203,30 @@ struct RiskState {
   const RiskRow* __restrict__ table;  // [B]
   int64_t O, D;                       // obstacles per problem; the draw period
 };
+struct MetricState {  // RiskState and the two pointers of the metric form
+  const drcvar_step_state* __restrict__ state;
+  int64_t path_last;
+  const RiskRow* __restrict__ table;
+  int64_t O, D;
+  const int32_t* __restrict__ metric;  // [B]
+  double* __restrict__ selected;       // [units, 4]
+};
 
 template <int BLOCK, int PP, int LOG_NB, bool ISO, bool DEV = false, bool PRED = false,
-          bool RISK = false>
+          bool RISK = false, bool METRIC = false>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BLOCK >= 512 ? 4 : 1)))
 sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __restrict__ ego,
                          DrawArgs a, Params prm, double* __restrict__ out,
                          int32_t* __restrict__ status, double* __restrict__ samples_out,
                          std::conditional_t<
-                             RISK, RiskState,
-                             std::conditional_t<PRED, PredState,
-                                                std::conditional_t<DEV, DevState, NoState>>> dev) {
+                             METRIC, MetricState,
+                             std::conditional_t<
+                                 RISK, RiskState,
+                                 std::conditional_t<PRED, PredState,
+                                                    std::conditional_t<DEV, DevState, NoState>>>> dev) {
   static_assert(DEV || !PRED, "the predicted-ego form is a device-state form");
   static_assert((DEV && !PRED) || !RISK, "the risk-table form is a device-state form without PRED");
+  static_assert(RISK || !METRIC, "the metric form is a risk-table form");
   constexpr int NW = BLOCK / kWave;
   constexpr int NB = 1 << LOG_NB;
   constexpr int Q = 2 * PP;  // sample slots per thread: 2 j the pair's first, 2 j + 1 its second
@@ -199,9 +247,11 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
   const int64_t u = a.u0 + row;
   const int64_t o = u / a.T, t = u - o * a.T;
   int64_t ud = u;  // the unit whose Philox counters are drawn
+  [[maybe_unused]] int32_t code = 0;  // METRIC: the problem's metric
   if constexpr (RISK) {
     const int64_t b = o / dev.O;
     prm = dev.table[b].p;
+    if constexpr (METRIC) code = dev.metric[b];
     ud = ((b % dev.D) * dev.O + (o - b * dev.O)) * a.T + t;
   }
   int64_t r = t;  // the unit's row of nominal[o] and of ego
@@ -311,7 +361,11 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
   if (bad || prm.unbounded) {  // risk_metrics.py:298-303,334-338
     if (tid == 0) {
       const double r = prm.rc * norm_h(h0, h1);
-      store_record(rec, mux, muy, prm.rc, h0, h1, failure_offsets(r));
+      if constexpr (METRIC)
+        store_record_selected(rec, dev.selected + row * DRCVAR_SEL_WIDTH, code, mux, muy, prm.rc,
+                              h0, h1, failure_offsets(r));
+      else
+        store_record(rec, mux, muy, prm.rc, h0, h1, failure_offsets(r));
       if (status) status[row] = failure_status(bad, prm);
     }
     return;  // uniform across the workgroup
@@ -406,7 +460,11 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
   // ---- 5. offsets (wave 0, lane 0) -------------------------------------------------------------
   if (lane == 0) {
     const double r = prm.rc * norm_h(h0, h1);  // R_c |h| (risk_metrics.py:293, :234)
-    store_record(rec, mux, muy, prm.rc, h0, h1, offsets_from_tail(prm, r, tau, dsum));
+    if constexpr (METRIC)
+      store_record_selected(rec, dev.selected + row * DRCVAR_SEL_WIDTH, code, mux, muy, prm.rc, h0,
+                            h1, offsets_from_tail(prm, r, tau, dsum));
+    else
+      store_record(rec, mux, muy, prm.rc, h0, h1, offsets_from_tail(prm, r, tau, dsum));
     if (status) status[row] = failure_status(false, prm);
   }
 }
@@ -452,6 +510,8 @@ struct Launch {
   hipStream_t stream;
   PredState pred;  // the predicted-ego form's arguments (state and path_last filled at launch)
   RiskState risk;  // the risk-table form's, likewise
+  const int32_t* metric;  // the metric form's two pointers
+  double* selected;
 };
 
 template <int BLOCK, int PP, int LOG_NB, bool ISO>
@@ -471,6 +531,12 @@ void launch_form(const Launch& L) {
   rs.path_last = L.path_last;
   hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true, false, true>), grid,
                      block, 0, L.stream, L.nominal, L.ego, L.a, L.prm, L.out, L.status, nullptr, rs);
+#elif defined(DRCVAR_LOOP_METRIC_LIBRARY)
+  // this library launches the metric form alone (L.prm is not read: the rows are the table's)
+  const MetricState ms{L.state, L.path_last, L.risk.table, L.risk.O, L.risk.D, L.metric, L.selected};
+  hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true, false, true, true>),
+                     grid, block, 0, L.stream, L.nominal, L.ego, L.a, L.prm, L.out, L.status,
+                     nullptr, ms);
 #else
   if (L.state)
     hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true>), grid, block, 0,
@@ -496,7 +562,8 @@ void launch_plan(Launch L) {
 // non-null selects the device-state form (n_steps is then the window length, path_steps the rows
 // of nominal and ego; stream_offset is unused, the kernel loads it).  `pred` non-null: the
 // predicted-ego form, which has no `ego`.  `risk` non-null: the risk-table form, whose five risk
-// scalars here are placeholders (its Params are the table's rows).
+// scalars here are placeholders (its Params are the table's rows).  `metric_form`: the metric form,
+// a risk-table form with `metric` and `selected`.
 int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_steps, int64_t nom_so,
                        int64_t nom_st, int64_t unit_begin, int64_t unit_count, int64_t n_samples,
                        double l00, double l10, double l11, uint64_t seed, uint64_t stream_offset,
@@ -505,7 +572,8 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
                        double robot_radius, double obstacle_radius, double alpha, double delta,
                        double epsilon, double* out, int32_t* status, double* samples_out, int64_t su,
                        int64_t sn, void* stream, const PredState* pred = nullptr,
-                       const RiskState* risk = nullptr) {
+                       const RiskState* risk = nullptr, bool metric_form = false,
+                       const int32_t* metric = nullptr, double* selected = nullptr) {
   if (n_obstacles < 0 || n_steps < 0 || n_samples < 0 || unit_begin < 0 || unit_count < 0)
     return DRCVAR_ERR_INVALID_ARGUMENT;
   if (dev && path_steps < 1) return DRCVAR_ERR_INVALID_ARGUMENT;
@@ -520,6 +588,7 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
   if (unit_begin > units || unit_count > units - unit_begin) return DRCVAR_ERR_INVALID_ARGUMENT;
   if (unit_count == 0 || n_samples == 0) return DRCVAR_OK;
   if (!nominal || (!ego && !pred) || !out) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (metric_form && (!metric || !selected)) return DRCVAR_ERR_INVALID_ARGUMENT;
   if (dev && (!state || reinterpret_cast<uintptr_t>(state) % 16 != 0))
     return DRCVAR_ERR_INVALID_ARGUMENT;
   if (unit_count > 0x7fffffffLL) return DRCVAR_ERR_UNSUPPORTED;  // one workgroup per unit: grid x
@@ -558,6 +627,8 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
   L.stream = static_cast<hipStream_t>(stream);
   if (pred) L.pred = *pred;
   if (risk) L.risk = *risk;
+  L.metric = metric;
+  L.selected = selected;
   (void)hipGetLastError();  // clear stale errors from unrelated work
   switch (pick_plan(n_samples)) {
     case 0: launch_plan<64, 1, 7>(L); break;
@@ -660,6 +731,33 @@ extern "C" int drcvar_sampled_halfspaces_f64_risk(
                             unit_count, n_samples, l00, l10, l11, seed, 0, state, true, path_steps,
                             zero_first_step, ego_path, ego_stride, 0.0, 0.0, 1.0, 0.0, 0.0, out,
                             status, nullptr, 0, 0, stream, nullptr, &rs);
+}
+#elif defined(DRCVAR_LOOP_METRIC_LIBRARY)
+// (the rows are drcvar_risk_table_fill's, made from this source: include/drcvar_loop_risk.h)
+extern "C" int64_t drcvar_metric_table_row_bytes(void) { return static_cast<int64_t>(sizeof(RiskRow)); }
+
+extern "C" int drcvar_sampled_halfspaces_f64_metric(
+    const double* nominal_path, int64_t n_obstacles, int64_t path_steps, int64_t nom_so,
+    int64_t nom_st, int64_t n_steps, int64_t unit_begin, int64_t unit_count, int64_t n_samples,
+    double l00, double l10, double l11, uint64_t seed, const drcvar_step_state* state,
+    int32_t zero_first_step, const double* ego_path, int64_t ego_stride,
+    int64_t n_obstacles_per_problem, const void* table, int64_t draw_period, const int32_t* metric,
+    double* out, int32_t* status, double* selected, void* stream) {
+  // the risk-table entry's checks, in its order; metric and selected beside nominal_path's
+  if (n_obstacles_per_problem < 1 || draw_period < 1) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (n_obstacles > 0 && n_obstacles % n_obstacles_per_problem != 0)
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  const bool launches = unit_count > 0 && n_samples > 0;
+  if (launches && (!table || reinterpret_cast<uintptr_t>(table) % 16 != 0))
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  RiskState rs{};
+  rs.table = static_cast<const RiskRow*>(table);
+  rs.O = n_obstacles_per_problem;
+  rs.D = draw_period;
+  return sampled_halfspaces(nominal_path, n_obstacles, n_steps, nom_so, nom_st, unit_begin,
+                            unit_count, n_samples, l00, l10, l11, seed, 0, state, true, path_steps,
+                            zero_first_step, ego_path, ego_stride, 0.0, 0.0, 1.0, 0.0, 0.0, out,
+                            status, nullptr, 0, 0, stream, nullptr, &rs, true, metric, selected);
 }
 #else
 extern "C" int drcvar_sampled_launch_plan(int64_t n_samples, int32_t* threads,

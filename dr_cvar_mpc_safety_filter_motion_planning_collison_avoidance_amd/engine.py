@@ -18,6 +18,8 @@ These are the batched calls everything else is built on:
 * :func:`sampled_halfspaces_risk` — ``drcvar_sampled_halfspaces_f64_risk``: that launch for a
   batch of loops, each unit's risk parameters taken from its own problem's row of a
   :class:`RiskTable`, the draws shared between problems by a draw period.
+* :func:`sampled_halfspaces_metric` — ``drcvar_sampled_halfspaces_f64_metric``: the risk-table
+  launch that also stores every unit's halfspace under its own problem's metric.
 
 All enqueue one kernel on the current HIP stream and return without synchronising.  Inputs must
 be float64 CUDA tensors whose two coordinates are adjacent (last stride 1); any other strides are
@@ -556,35 +558,11 @@ class RiskTable:
         return torch.from_numpy(host).to(device)
 
 
-def prepare_sampled_halfspaces_risk(nominal_path: torch.Tensor, ego_path: torch.Tensor,
-                                    n_obstacles: int, n_steps: int, n_samples: int,
-                                    params: RiskTable, state: torch.Tensor, *,
-                                    draw_period: int | None = None, table: torch.Tensor | None = None,
-                                    noise_cov=DEFAULT_NOISE_COV, seed: int = 0,
-                                    zero_first_step: bool = True, unit_begin: int = 0,
-                                    unit_count: int | None = None, out: torch.Tensor | None = None,
-                                    status: torch.Tensor | None = None, stream=None,
-                                    chol=None) -> tuple[PreparedLaunch, torch.Tensor]:
-    """Freeze one ``drcvar_sampled_halfspaces_f64_risk`` call (``include/drcvar_loop_risk.h``):
-    :func:`prepare_sampled_halfspaces_dev` for B problems of ``n_obstacles`` = O obstacles each,
-    with the risk parameters of every unit taken from its own problem's row of ``params`` (a
-    :class:`RiskTable` of B rows) and draws shared between problems by ``draw_period``.
-
-    nominal_path ``[B O, P, 2]`` (problem b's obstacles are rows ``b O .. b O + O - 1``) and
-    ego_path ``[P, 2]`` as in :func:`prepare_sampled_halfspaces_dev`.  Unit ``u = (b O + o) T + t``
-    takes what that entry's unit takes, but filters with ``params.row(b)`` and draws the Philox
-    counters of unit ``((b mod D) O + o) T + t``, ``D = draw_period`` (None: B, the entry's own
-    draws; 1: every problem meets problem 0's draws; B = S D with ``b = s D + r``: S settings on
-    the same D replicate draws).  Per problem the records and status words are bit for bit those of
-    :func:`sampled_halfspaces` on a nominal tensor whose rows ``(b mod D) O .. + O`` are the
-    problem's gathered window, with the gathered ego window, ``unit_begin = (b mod D) O T``,
-    ``unit_count = O T``, the state's offset and ``params.row(b)``.
-
-    ``table`` (optional): ``params.to_device(n_samples, device)`` made earlier, so that several
-    launches share one copy; the entry cannot check device memory, so the table is only accepted
-    with the shape that ``params`` and the library give it.  ``out`` is ``[B O, n_steps, 8]``, or
-    ``[unit_count, 8]`` for a unit window; ``status``, ``stream`` and ``chol`` as in
-    :func:`prepare_sampled_halfspaces_dev`."""
+def _risk_launch_setup(nominal_path, ego_path, n_obstacles, n_steps, n_samples, params, state,
+                       draw_period, table, noise_cov, unit_begin, unit_count, out, status, chol):
+    """The checks and launch-uniform values that the risk-table and the metric launch share
+    (:func:`prepare_sampled_halfspaces_risk`): ``(dev, BO, P, O, B, D, T, n, u0, count, whole, out,
+    table, (l00, l10, l11))``."""
     if not isinstance(params, RiskTable):
         raise ValueError("params must be a RiskTable")
     params.validate()
@@ -630,6 +608,41 @@ def prepare_sampled_halfspaces_risk(nominal_path: torch.Tensor, ego_path: torch.
         raise ValueError(f"table must be a contiguous, 16-byte aligned uint8 [{B}, {row}] tensor on "
                          f"{dev} (RiskTable.to_device)")
     l00, l10, l11 = _noise_factor(noise_cov, chol)
+    return dev, BO, P, O, B, D, T, n, u0, count, whole, out, table, (l00, l10, l11)
+
+
+def prepare_sampled_halfspaces_risk(nominal_path: torch.Tensor, ego_path: torch.Tensor,
+                                    n_obstacles: int, n_steps: int, n_samples: int,
+                                    params: RiskTable, state: torch.Tensor, *,
+                                    draw_period: int | None = None, table: torch.Tensor | None = None,
+                                    noise_cov=DEFAULT_NOISE_COV, seed: int = 0,
+                                    zero_first_step: bool = True, unit_begin: int = 0,
+                                    unit_count: int | None = None, out: torch.Tensor | None = None,
+                                    status: torch.Tensor | None = None, stream=None,
+                                    chol=None) -> tuple[PreparedLaunch, torch.Tensor]:
+    """Freeze one ``drcvar_sampled_halfspaces_f64_risk`` call (``include/drcvar_loop_risk.h``):
+    :func:`prepare_sampled_halfspaces_dev` for B problems of ``n_obstacles`` = O obstacles each,
+    with the risk parameters of every unit taken from its own problem's row of ``params`` (a
+    :class:`RiskTable` of B rows) and draws shared between problems by ``draw_period``.
+
+    nominal_path ``[B O, P, 2]`` (problem b's obstacles are rows ``b O .. b O + O - 1``) and
+    ego_path ``[P, 2]`` as in :func:`prepare_sampled_halfspaces_dev`.  Unit ``u = (b O + o) T + t``
+    takes what that entry's unit takes, but filters with ``params.row(b)`` and draws the Philox
+    counters of unit ``((b mod D) O + o) T + t``, ``D = draw_period`` (None: B, the entry's own
+    draws; 1: every problem meets problem 0's draws; B = S D with ``b = s D + r``: S settings on
+    the same D replicate draws).  Per problem the records and status words are bit for bit those of
+    :func:`sampled_halfspaces` on a nominal tensor whose rows ``(b mod D) O .. + O`` are the
+    problem's gathered window, with the gathered ego window, ``unit_begin = (b mod D) O T``,
+    ``unit_count = O T``, the state's offset and ``params.row(b)``.
+
+    ``table`` (optional): ``params.to_device(n_samples, device)`` made earlier, so that several
+    launches share one copy; the entry cannot check device memory, so the table is only accepted
+    with the shape that ``params`` and the library give it.  ``out`` is ``[B O, n_steps, 8]``, or
+    ``[unit_count, 8]`` for a unit window; ``status``, ``stream`` and ``chol`` as in
+    :func:`prepare_sampled_halfspaces_dev`."""
+    dev, BO, P, O, B, D, T, n, u0, count, whole, out, table, (l00, l10, l11) = _risk_launch_setup(
+        nominal_path, ego_path, n_obstacles, n_steps, n_samples, params, state, draw_period, table,
+        noise_cov, unit_begin, unit_count, out, status, chol)
     args = (ctypes.c_void_p(nominal_path.data_ptr()), BO, P, nominal_path.stride(0),
             nominal_path.stride(1), T, u0, count, n, l00, l10, l11,
             ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), ctypes.c_void_p(state.data_ptr()),
@@ -654,6 +667,116 @@ def sampled_halfspaces_risk(nominal_path: torch.Tensor, ego_path: torch.Tensor, 
     if out.numel() > 0:
         launch()
     return out
+
+
+METRIC_CODES = {"mean": 0, "cvar": 1, "dr_cvar": 2}   # DRCVAR_METRIC_* (include/drcvar_loop_metric.h)
+SELECTED_WIDTH = 4                                    # DRCVAR_SEL_WIDTH
+
+
+def metric_codes(metric, n_problems: int, device) -> torch.Tensor:
+    """The names ``metric`` (a sequence of ``n_problems`` keys of :data:`METRIC_CODES`) as the
+    int32 ``[B]`` tensor on ``device`` that the metric launch reads."""
+    if isinstance(metric, str) or not hasattr(metric, "__len__"):
+        raise ValueError("metric must be a sequence of names, one per problem")
+    names = list(metric)
+    if len(names) != int(n_problems):
+        raise ValueError(f"metric has {len(names)} names, the launch {n_problems} problems")
+    unknown = [m for m in names if not isinstance(m, str) or m not in METRIC_CODES]
+    if unknown:
+        raise ValueError(f"metric names must be among {tuple(METRIC_CODES)}, got {unknown[0]!r}")
+    return torch.tensor([METRIC_CODES[m] for m in names], dtype=torch.int32).to(device)
+
+
+def prepare_sampled_halfspaces_metric(nominal_path: torch.Tensor, ego_path: torch.Tensor,
+                                      n_obstacles: int, n_steps: int, n_samples: int,
+                                      params: RiskTable, metric, state: torch.Tensor, *,
+                                      draw_period: int | None = None,
+                                      table: torch.Tensor | None = None,
+                                      codes: torch.Tensor | None = None,
+                                      noise_cov=DEFAULT_NOISE_COV, seed: int = 0,
+                                      zero_first_step: bool = True, unit_begin: int = 0,
+                                      unit_count: int | None = None, out: torch.Tensor | None = None,
+                                      selected: torch.Tensor | None = None,
+                                      status: torch.Tensor | None = None, stream=None, chol=None
+                                      ) -> tuple[PreparedLaunch, torch.Tensor, torch.Tensor]:
+    """Freeze one ``drcvar_sampled_halfspaces_f64_metric`` call (``include/drcvar_loop_metric.h``):
+    :func:`prepare_sampled_halfspaces_risk` whose launch also writes, for every unit, the halfspace
+    under its own problem's metric.  Returns ``(launch, out, selected)``.
+
+    ``metric`` is a sequence of B names among :data:`METRIC_CODES`.  ``out`` and ``status`` are
+    byte for byte what :func:`prepare_sampled_halfspaces_risk` gives for the same arguments;
+    ``selected`` is ``[B O, n_steps, 4]`` (``[unit_count, 4]`` for a unit window): for a unit of
+    problem b the columns ``core/mpc_filter.METRIC_COLUMNS[metric[b]]`` of its record, then +0.0,
+    stored by the lane that stores the record (:func:`selected_views` gives the solver's views).
+
+    ``codes`` (optional): ``metric_codes(metric, B, device)`` made earlier, as ``table`` is for the
+    rows; the entry cannot check device memory, so it is only accepted as an int32 ``[B]`` tensor
+    on the device.  Everything else: :func:`prepare_sampled_halfspaces_risk`."""
+    if isinstance(nominal_path, torch.Tensor) and nominal_path.dim() == 3 and int(n_obstacles) >= 1 \
+            and nominal_path.shape[0] % int(n_obstacles) == 0:
+        # what the host alone can tell about metric, codes and selected, before anything else: the
+        # names, and the shapes the kernel would read and write through the raw pointers
+        rows, B = nominal_path.shape[0], nominal_path.shape[0] // int(n_obstacles)
+        metric_codes(metric, B, "cpu")
+        if codes is not None and (not isinstance(codes, torch.Tensor) or codes.dtype != torch.int32
+                                  or tuple(codes.shape) != (B,) or not codes.is_contiguous()):
+            raise ValueError(f"codes must be a contiguous int32 [{B}] tensor (metric_codes)")
+        if selected is not None:
+            if unit_count is None and int(unit_begin) == 0:
+                shape = (rows, int(n_steps), SELECTED_WIDTH)
+            else:
+                shape = (rows * int(n_steps) - int(unit_begin) if unit_count is None else int(unit_count),
+                         SELECTED_WIDTH)
+            if not isinstance(selected, torch.Tensor) or tuple(selected.shape) != shape or \
+                    selected.dtype != torch.float64 or not selected.is_contiguous():
+                raise ValueError(f"selected must be a contiguous float64 {list(shape)} tensor")
+    dev, BO, P, O, B, D, T, n, u0, count, whole, out, table, (l00, l10, l11) = _risk_launch_setup(
+        nominal_path, ego_path, n_obstacles, n_steps, n_samples, params, state, draw_period, table,
+        noise_cov, unit_begin, unit_count, out, status, chol)
+    if codes is None:
+        codes = metric_codes(metric, B, dev)
+    elif codes.device != dev:
+        raise ValueError(f"codes must live on {dev}")
+    if selected is None:
+        selected = torch.empty((BO, T, SELECTED_WIDTH) if whole else (count, SELECTED_WIDTH),
+                               dtype=torch.float64, device=dev)
+    elif selected.device != dev:
+        raise ValueError(f"selected must live on {dev}")
+    lib = _native.metric_lib()
+    args = (ctypes.c_void_p(nominal_path.data_ptr()), BO, P, nominal_path.stride(0),
+            nominal_path.stride(1), T, u0, count, n, l00, l10, l11,
+            ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), ctypes.c_void_p(state.data_ptr()),
+            ctypes.c_int32(1 if zero_first_step else 0),
+            ctypes.c_void_p(ego_path.data_ptr()), ego_path.stride(0), O,
+            ctypes.c_void_p(table.data_ptr()), D, ctypes.c_void_p(codes.data_ptr()),
+            ctypes.c_void_p(out.data_ptr()),
+            ctypes.c_void_p(status.data_ptr() if status is not None else None),
+            ctypes.c_void_p(selected.data_ptr()), ctypes.c_void_p(_stream_handle(dev, stream)))
+    launch = PreparedLaunch(lib.drcvar_sampled_halfspaces_f64_metric, args,
+                            (nominal_path, ego_path, state, table, codes, out, status, selected))
+    return launch, out, selected
+
+
+def sampled_halfspaces_metric(nominal_path: torch.Tensor, ego_path: torch.Tensor, n_obstacles: int,
+                              n_steps: int, n_samples: int, params: RiskTable, metric,
+                              state: torch.Tensor, **kwargs) -> tuple[torch.Tensor, torch.Tensor]:
+    """One ``drcvar_sampled_halfspaces_f64_metric`` launch (arguments:
+    :func:`prepare_sampled_halfspaces_metric`): returns ``(out, selected)``."""
+    launch, out, selected = prepare_sampled_halfspaces_metric(
+        nominal_path, ego_path, n_obstacles, n_steps, n_samples, params, metric, state, **kwargs)
+    if out.numel() > 0:
+        launch()
+    return out, selected
+
+
+def selected_views(selected: torch.Tensor, n_problems: int, n_obstacles: int):
+    """``(h [B, O, T, 2], g [B, O, T])``: the solver's halfspace views of a whole-window
+    ``selected [B O, T, 4]``, strided, no copy."""
+    B, O = int(n_problems), int(n_obstacles)
+    if selected.dim() != 3 or selected.shape[0] != B * O or selected.shape[2] != SELECTED_WIDTH:
+        raise ValueError(f"selected must be [{B * O}, T, {SELECTED_WIDTH}], got {tuple(selected.shape)}")
+    v = selected.view(B, O, selected.shape[1], SELECTED_WIDTH)
+    return v[..., 0:2], v[..., 2]
 
 
 def offsets_given_h(samples: torch.Tensor, h: torch.Tensor, params: RiskParams = RiskParams(),

@@ -42,6 +42,12 @@ with its OWN (alpha, delta, epsilon), launch 1 being ``drcvar_sampled_halfspaces
 (``include/drcvar_loop_risk.h``), and ``draw_period=D`` gives problems ``b`` and
 ``b + D`` the same draws, so a grid of settings x D replicates is one batch on common random
 numbers.  With a ``RiskParams`` nothing changes.
+
+``RecedingHorizonBatch(metric=[...])``, one name per problem, gives every loop its OWN metric:
+launch 1 is then ``drcvar_sampled_halfspaces_f64_metric`` (``include/drcvar_loop_metric.h``,
+DESIGN.md §5.8), the risk-table launch whose storing lane also writes each unit's chosen halfspace,
+and the solve reads those: mean, CVaR and DR-CVaR are compared on common random numbers in one
+batch.  With a string metric nothing changes.
 """
 from __future__ import annotations
 
@@ -315,6 +321,32 @@ def check_risk(params, draw_period, n_problems, linearize):
     return int(draw_period)
 
 
+def check_metric(metric, n_problems, linearize):
+    """The ``metric=`` argument of the loop classes (host only).  A name returns None (today's
+    path); a sequence of ``n_problems`` names returns them as a tuple; ``n_problems=None`` is the
+    single-loop class, which takes a name only."""
+    if isinstance(metric, str):
+        if metric not in METRIC_COLUMNS:
+            raise ValueError(f"metric must be one of {tuple(METRIC_COLUMNS)}, got {metric!r}")
+        return None
+    try:
+        names = tuple(metric)
+    except TypeError:
+        raise ValueError(f"metric must be one of {tuple(METRIC_COLUMNS)} or a sequence of them, "
+                         f"got {metric!r}") from None
+    if n_problems is None:
+        raise ValueError("a sequence of metrics belongs to RecedingHorizonBatch; "
+                         "RecedingHorizonFilter takes one name")
+    if linearize == "predicted":
+        raise ValueError('a sequence of metrics cannot be combined with linearize="predicted"')
+    if len(names) != int(n_problems):
+        raise ValueError(f"metric has {len(names)} names, n_problems={n_problems}")
+    for name in names:
+        if not isinstance(name, str) or name not in engine.METRIC_CODES:
+            raise ValueError(f"metric names must be among {tuple(engine.METRIC_CODES)}, got {name!r}")
+    return names
+
+
 class _Linearized:
     """What the two loop classes share for ``linearize="predicted"``: the
     halfspaces of window row t are taken about the loop's own prediction for that path time
@@ -398,8 +430,7 @@ class RecedingHorizonFilter(_Evaluated, _Linearized):
                  zero_first_step=True, max_iter=DEFAULT_MAX_ITER, tol=DEFAULT_TOL, polish=True,
                  options=None, disturbance=None, steps_per_graph=1, evaluate=None,
                  linearize="reference", relinearize=0):
-        if metric not in METRIC_COLUMNS:
-            raise ValueError(f"metric must be one of {tuple(METRIC_COLUMNS)}, got {metric!r}")
+        check_metric(metric, None, linearize)       # (a sequence of metrics is the batch class's)
         if int(steps_per_graph) < 1:
             raise ValueError(f"steps_per_graph={steps_per_graph} must be at least 1")
         check_evaluate(evaluate)
@@ -704,8 +735,8 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
     so the problems get independent draws from the one ``seed`` and stream offset, and with B = 1
     the loop is :class:`RecedingHorizonFilter`'s, bit for bit.  With ``linearize="reference"`` the
     records do not depend on ``metric``: batches built with the same seed, offset and paths see
-    the same halfspace records at equal steps, so mean, CVaR and DR-CVaR are compared on common
-    random numbers by running three batches (there is no per-problem metric).  With
+    the same halfspace records at equal steps, so mean, CVaR and DR-CVaR can be compared on common
+    random numbers by running three batches, or as one batch with a metric per problem (below).  With
     ``linearize="predicted"`` (:class:`RecedingHorizonFilter`; step 1 is then
     ``drcvar_sampled_halfspaces_f64_pred`` on ``x0 [B, nx]`` and ``x_out [B, H + 1, nx]``, and
     problems that differ in ``x0`` or disturbance get different halfspaces) the records follow each
@@ -723,6 +754,19 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
     ``linearize="predicted"``, one whose length is not B, or a ``draw_period`` beside a
     ``RiskParams`` is a ``ValueError``; with a ``RiskParams`` the batch is what it was.
 
+    ``metric`` may be a sequence of B names: every loop then filters under its OWN metric
+    (``metrics`` holds the B names; with a string it is that name B times).  Step 1 is one
+    ``drcvar_sampled_halfspaces_f64_metric`` launch (``include/drcvar_loop_metric.h``, DESIGN.md
+    §5.8): the risk-table launch, whose storing lane also writes the unit's chosen ``(h0, h1, g,
+    0)`` into ``[B O, H, 4]``; step 2 solves on ``engine.selected_views`` of that.  ``params`` may
+    then be a ``RiskTable`` or a ``RiskParams`` (taken as a table of B equal rows; ``params`` then
+    holds that table), ``draw_period`` is allowed with either, and S metrics x D replicates with
+    ``b = s D + r`` and ``draw_period=D`` is the three-metric comparison on common random numbers
+    as one batch.  The ``reference`` backend gathers each problem's columns from the per-problem
+    records with torch indexing.  A sequence whose length is not B, an unknown name, or a sequence
+    with ``linearize="predicted"`` is a ``ValueError``; with a string the batch is what it was,
+    launch for launch.
+
     ``reset(x0)`` takes ``[B, nx]`` or ``[nx]``.  ``run(n, backend)`` returns ``(states [B, n + 1,
     nx], inputs [B, n, nu], info [B, n, 10])``; backends, log capacity, rebasing, the limit of D
     steps per reset under a disturbance and the treatment of failed solves (a logged step; nothing
@@ -736,12 +780,17 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
                  zero_first_step=True, max_iter=DEFAULT_MAX_ITER, tol=DEFAULT_TOL, polish=True,
                  options=None, disturbance=None, steps_per_graph=1, evaluate=None,
                  linearize="reference", relinearize=0, draw_period=None):
-        if metric not in METRIC_COLUMNS:
-            raise ValueError(f"metric must be one of {tuple(METRIC_COLUMNS)}, got {metric!r}")
+        names = check_metric(metric, n_problems, linearize)
         if int(steps_per_graph) < 1:
             raise ValueError(f"steps_per_graph={steps_per_graph} must be at least 1")
         check_evaluate(evaluate)
         check_linearize(linearize, relinearize)
+        if names is not None and not isinstance(params, engine.RiskTable):
+            # a metric per problem rides on the risk-table launch: B equal rows
+            params.validate()
+            params = engine.RiskTable(alpha=[params.alpha] * len(names), delta=params.delta,
+                                      epsilon=params.epsilon, robot_radius=params.robot_radius,
+                                      obstacle_radius=params.obstacle_radius)
         self.draw_period = check_risk(params, draw_period, n_problems, linearize)
         n = int(n_samples)
         if n < 1 or n > _native.MAX_SAMPLES:
@@ -758,6 +807,7 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
             if t is not None and t.device != dev:
                 raise ValueError(f"{name} must live on the model's device {dev}, got {t.device}")
         self.model, self.params, self.metric = model, params, metric
+        self.metrics = names if names is not None else (metric,) * B
         self.n_problems, self.n_obstacles = B, O
         self.n_samples, self.seed = n, int(seed) & _MASK64
         self.noise_cov, self.chol, self.zero_first_step = noise_cov, chol, bool(zero_first_step)
@@ -788,6 +838,12 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         self._lin_init(linearize, relinearize, B, O, self.nominal_path)
         # a RiskTable: filled for n_samples and copied to the device once
         self._risk_table = params.to_device(n, dev) if self.draw_period is not None else None
+        # a metric per problem: the codes on the device, and what the solve reads in place of
+        # record columns
+        self._codes = self._selected = None
+        if names is not None:
+            self._codes = engine.metric_codes(names, B, dev)
+            self._selected = torch.zeros((B * O, H, engine.SELECTED_WIDTH), **f64)
         self._logs = None           # (x_log [B, cap + 1, nx], u_log [B, cap, nu], info_log [B, cap, 10])
         self._cap, self._step_begin = 0, 0
         self._primed = False
@@ -860,6 +916,13 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         if self.linearize == "predicted":
             halfspaces = self._lin_launch(stream, 1)
             again = self._lin_launch(stream, 0) if self.relinearize else None
+        elif self._codes is not None:
+            halfspaces, _, _ = engine.prepare_sampled_halfspaces_metric(
+                self.nominal_path, self.ego_path, self.n_obstacles, H, self.n_samples, self.params,
+                self.metrics, self._state[0], draw_period=self.draw_period, table=self._risk_table,
+                codes=self._codes, noise_cov=self.noise_cov, seed=self.seed,
+                zero_first_step=self.zero_first_step, out=self._record, selected=self._selected,
+                stream=stream, chol=self.chol)
         elif self._risk_table is not None:
             halfspaces, _ = engine.prepare_sampled_halfspaces_risk(
                 self.nominal_path, self.ego_path, self.n_obstacles, H, self.n_samples, self.params,
@@ -871,7 +934,10 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
                 self.nominal_path, self.ego_path, H, self.n_samples, self.params, self._state[0],
                 noise_cov=self.noise_cov, seed=self.seed, zero_first_step=self.zero_first_step,
                 out=self._record, stream=stream, chol=self.chol)
-        hs_h, hs_g = self._views(self._record)
+        if self._codes is not None:
+            hs_h, hs_g = engine.selected_views(self._selected, self.n_problems, self.n_obstacles)
+        else:
+            hs_h, hs_g = self._views(self._record)
         vp = ctypes.c_void_p
         x_log, u_log, info_log = self._logs
         dist = self.disturbance
@@ -931,6 +997,17 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
                 zero_first_step=self.zero_first_step, unit_begin=r * O * H, unit_count=O * H))
         return torch.cat(records).view(B * O, H, engine.OUT_WIDTH)
 
+    def _reference_selected(self, record):
+        """``[B O, H, 4]``: each problem's ``METRIC_COLUMNS`` gathered from ``record`` with torch
+        indexing, the fourth column zero (what the metric launch stores beside the record)."""
+        B, O = self.n_problems, self.n_obstacles
+        cols = torch.tensor([[c, c + 1, g] for c, g in (METRIC_COLUMNS[m] for m in self.metrics)],
+                            device=record.device).repeat_interleave(O, dim=0)      # [B O, 3]
+        selected = torch.zeros((B * O, record.shape[1], engine.SELECTED_WIDTH), dtype=record.dtype,
+                               device=record.device)
+        selected[..., :3] = record.gather(2, cols[:, None, :].expand(-1, record.shape[1], -1))
+        return selected
+
     def _reference_step(self, i):
         m = self.model
         H, B = m.horizon, self.n_problems
@@ -948,7 +1025,11 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
                                                    noise_cov=self.noise_cov, chol=self.chol,
                                                    seed=self.seed, stream_offset=self._offset,
                                                    zero_first_step=self.zero_first_step)
-            hs_h, hs_g = self._views(record)
+            if self._codes is not None:
+                hs_h, hs_g = engine.selected_views(self._reference_selected(record), B,
+                                                   self.n_obstacles)
+            else:
+                hs_h, hs_g = self._views(record)
             x, u, info = filter_batch(m, hs_h, hs_g, self._x0, self._x_ref_win, self._u_fb,
                                       self.max_iter, self.tol, self.polish, options=self.options)
             self._x.copy_(x)   # (the next linearisation point; the device backends' x_out)
