@@ -184,6 +184,16 @@ constexpr double kStartFloorW = 1e-2;     // smallest starting slack of a bound 
 constexpr int kResumeIters = 8;         // interior-point iterations after a failed polish
 constexpr double kResumeTol = 1e-3;     // ... towards tol * kResumeTol
 constexpr double kPolishEqTol = 1e-12;  // multiplier passes stop at |E u - e| <= this * (1 + max|g|)
+// A set whose equalities are nearly dependent (the position box binding over consecutive steps of a
+// long horizon: E H^-1 E' down to 5e-7, so a pass closes only a third of the residual) is not
+// solved after kPolishIters passes: |E u - e| ~ 2e-9 there left u 2e-6 from the optimum, and the
+// sign conditions, read at that u, accepted it as polished (tests/test_mpc_bounds_gpu.py, double
+// integrator, H = 33, position box alone).  Past kPolishIters the passes go on, to kPolishMaxIters
+// at most, while the residual is above kPolishLateTol * (1 + max|g|) and still falls by a tenth per
+// pass; a guess is accepted only with its equalities closed to kPolishLateTol.
+constexpr int kPolishMaxIters = 48;
+constexpr double kPolishLateTol = 1e-11;
+constexpr double kPolishLateGain = 0.9;
 
 // clustered form (see cluster_combine)
 constexpr int kClusterMaxProblems = 8;
@@ -2816,7 +2826,8 @@ __global__ __launch_bounds__(BLK, (CL && BLK <= 256) ? 1 : 2) void mpc_ipm_kerne
       // carries both its residual maximum and those sums (`carried`): one cluster exchange per
       // pass instead of two, the same sums in the same order.
       bool carried = false;
-      for (int pass = 0; pass < kPolishIters; ++pass) {
+      double eres_end = 0.0, eres_prev = kHuge;  // uniform (eres is reduced over the block / cluster)
+      for (int pass = 0; pass < kPolishMaxIters; ++pass) {
         // rhs = -f - sum_pen (50 + 100 b) a - E'(nu - rho e), per step through Gp'
         double acc[2] = {0, 0};
         if (!carried && lane < K) {
@@ -2939,7 +2950,11 @@ __global__ __launch_bounds__(BLK, (CL && BLK <= 256) ? 1 : 2) void mpc_ipm_kerne
         double unused_a = 0.0, unused_b = 0.0;
         block_sum_max_max<kWaves>(unused_a, eres, unused_b, s.sc);  // uniform; also the barrier
         CL_NOTE(eres);
+        eres_end = eres;
         if (eres <= kPolishEqTol * scale_d) break;
+        if (pass + 1 >= kPolishIters &&
+            (eres <= kPolishLateTol * scale_d || eres > kPolishLateGain * eres_prev)) break;
+        eres_prev = eres;
         carried = true;
       }
       // sign conditions; violators move (primal-dual active-set step).  Rows that must become
@@ -3048,7 +3063,9 @@ __global__ __launch_bounds__(BLK, (CL && BLK <= 256) ? 1 : 2) void mpc_ipm_kerne
       }
       bad = block_sum<kWaves>(bad, s.sc);
       CL_NOTE(bad);
-      if (bad == 0.0) polished = true;
+      // the sign conditions hold at a u that solves the set's equalities (else: another attempt
+      // with the same set goes on from these multipliers)
+      if (bad == 0.0 && eres_end <= kPolishLateTol * scale_d) polished = true;
     }
     if (polished) {
       status = DRCVAR_MPC_STATUS_OPTIMAL;
