@@ -3,8 +3,8 @@
 bound with ctypes; beside it the loop library (``drcvar_loop.h``, :func:`loop_lib`), the
 loop-evaluation library (``drcvar_loop_eval.h``, :func:`eval_lib`), the predicted-ego library
 (``drcvar_loop_pred.h``, :func:`pred_lib`), the risk-table library (``drcvar_loop_risk.h``,
-:func:`risk_lib`) and the metric library (``drcvar_loop_metric.h``, :func:`metric_lib`), one entry
-family each.
+:func:`risk_lib`), the metric library (``drcvar_loop_metric.h``, :func:`metric_lib`) and the route
+library (``drcvar_loop_route.h``, :func:`route_lib`), one entry family each.
 
 There is deliberately no fallback: if the shared library is missing or cannot be loaded every
 entry point raises :class:`NativeLibraryError`.  ``build()`` compiles it for gfx950 in-tree.
@@ -65,6 +65,14 @@ METRIC_LIB_PATH = os.path.join(LIB_DIR, "libdrcvar_loop_metric.so")
 METRIC_HEADER = os.path.join(INCLUDE_DIR, "drcvar_loop_metric.h")
 METRIC_UNIT = (os.path.join(PKG_DIR, "csrc", "drcvar_sampled.hip"), ("-DDRCVAR_LOOP_METRIC_LIBRARY",))
 METRIC_SYMBOLS = ("drcvar_metric_table_row_bytes", "drcvar_sampled_halfspaces_f64_metric")
+# The route library (include/drcvar_loop_route.h): two objects in one library, csrc/drcvar_sampled.hip
+# compiled a fifth time and csrc/drcvar_step.hip a third time, both with DRCVAR_LOOP_ROUTE_LIBRARY (the
+# 14 kernels of the route form and the route advance kernel, none of the other libraries').
+ROUTE_LIB_PATH = os.path.join(LIB_DIR, "libdrcvar_loop_route.so")
+ROUTE_HEADER = os.path.join(INCLUDE_DIR, "drcvar_loop_route.h")
+ROUTE_UNIT = ((os.path.join(PKG_DIR, "csrc", "drcvar_sampled.hip"), ("-DDRCVAR_LOOP_ROUTE_LIBRARY",)),
+              (os.path.join(PKG_DIR, "csrc", "drcvar_step.hip"), ("-DDRCVAR_LOOP_ROUTE_LIBRARY",)))
+ROUTE_SYMBOLS = ("drcvar_sampled_halfspaces_f64_route", "drcvar_mpc_step_advance_batch_route_f64")
 
 ABI_VERSION = 3
 OUT_WIDTH = 8
@@ -292,11 +300,12 @@ def build(verbose: bool = False, extra_flags=()) -> str:
     import glob
     incs = sorted(glob.glob(os.path.join(PKG_DIR, "csrc", "*.inc")))  # tables the sources include
     headers = b"".join(open(h, "rb").read() for h in HEADERS + [LOOP_HEADER, EVAL_HEADER, PRED_HEADER, RISK_HEADER,
-                                                                   METRIC_HEADER] + incs)
+                                                                   METRIC_HEADER, ROUTE_HEADER] + incs)
     # the compiler's identity is part of every key: objects of an older hipcc / ROCm are rebuilt
     toolchain = _toolchain(probe=True)
     objs, procs = [], []
-    for src, defs in _compile_units() + [LOOP_UNIT, EVAL_UNIT, PRED_UNIT, RISK_UNIT, METRIC_UNIT]:
+    for src, defs in _compile_units() + [LOOP_UNIT, EVAL_UNIT, PRED_UNIT, RISK_UNIT, METRIC_UNIT,
+                                         *ROUTE_UNIT]:
         flags = _unit_flags(defs, extra_flags)
         key = hashlib.sha256(open(src, "rb").read() + headers + toolchain
                              + " ".join(flags).encode()).hexdigest()[:16]
@@ -314,11 +323,12 @@ def build(verbose: bool = False, extra_flags=()) -> str:
         raise subprocess.CalledProcessError(1, failed[0])
     for _, obj, _ in procs:
         os.replace(obj + ".tmp", obj)
-    # (LOOP_UNIT, EVAL_UNIT, PRED_UNIT, RISK_UNIT and METRIC_UNIT are the last five: each is a
-    # library of its own)
-    for path, members in ((LIB_PATH, objs[:-5]), (LOOP_LIB_PATH, objs[-5:-4]),
-                          (EVAL_LIB_PATH, objs[-4:-3]), (PRED_LIB_PATH, objs[-3:-2]),
-                          (RISK_LIB_PATH, objs[-2:-1]), (METRIC_LIB_PATH, objs[-1:])):
+    # (LOOP_UNIT, EVAL_UNIT, PRED_UNIT, RISK_UNIT and METRIC_UNIT come after the engine's objects,
+    # each a library of its own; ROUTE_UNIT's two objects are the last two, one library)
+    for path, members in ((LIB_PATH, objs[:-7]), (LOOP_LIB_PATH, objs[-7:-6]),
+                          (EVAL_LIB_PATH, objs[-6:-5]), (PRED_LIB_PATH, objs[-5:-4]),
+                          (RISK_LIB_PATH, objs[-4:-3]), (METRIC_LIB_PATH, objs[-3:-2]),
+                          (ROUTE_LIB_PATH, objs[-2:])):
         link = ["hipcc", f"--offload-arch={OFFLOAD_ARCH}", "-shared", "-fPIC", *members,
                 "-o", path + ".tmp"]
         if verbose:
@@ -612,6 +622,40 @@ def metric_lib():
                     f"rows of {rows[1]}: the two libraries are not of one build")
             _metric_lib = handle
     return _metric_lib
+
+
+_route_lib = None
+
+
+def route_lib():
+    """The loaded route library (``include/drcvar_loop_route.h``; raises NativeLibraryError if it
+    is not built: there is no fallback).  It shares the engine library's structs and return codes
+    and reads the rows the risk-table library fills."""
+    global _route_lib
+    if _route_lib is not None:
+        return _route_lib
+    with _lock:
+        if _route_lib is None:
+            if not os.path.exists(ROUTE_LIB_PATH):
+                raise NativeLibraryError(
+                    f"route library not built: {ROUTE_LIB_PATH} is missing (run "
+                    f"__graft_entry__.build())")
+            try:
+                handle = ctypes.CDLL(ROUTE_LIB_PATH)
+            except OSError as exc:  # pragma: no cover - depends on the ROCm install
+                raise NativeLibraryError(f"cannot load {ROUTE_LIB_PATH}: {exc}") from exc
+            i64, i32, dbl, u64, ptr = (ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                                       ctypes.c_uint64, ctypes.c_void_p)
+            handle.drcvar_sampled_halfspaces_f64_route.argtypes = [
+                ptr, i64, i64, i64, i64, i64, i64, i64, i64, dbl, dbl, dbl, u64, ptr, i32,
+                ptr, i64, i64, i64, ptr, i64, ptr, ptr, ptr, ptr, ptr]
+            handle.drcvar_sampled_halfspaces_f64_route.restype = ctypes.c_int
+            handle.drcvar_mpc_step_advance_batch_route_f64.argtypes = [
+                ctypes.POINTER(MpcModel), i64, ptr, ptr, ptr, ptr, ptr, i64, i64, i64, ptr, i64, i64,
+                ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
+            handle.drcvar_mpc_step_advance_batch_route_f64.restype = ctypes.c_int
+            _route_lib = handle
+    return _route_lib
 
 
 def check(code: int) -> None:

@@ -26,7 +26,7 @@
 //
 // samples_out (optional): the kernel also stores the samples it drew; the record is the same bits.
 //
-// Five entries, one kernel template: drcvar_sampled_halfspaces_f64 freezes the stream offset and
+// Six entries, one kernel template: drcvar_sampled_halfspaces_f64 freezes the stream offset and
 // the window in its arguments; drcvar_sampled_halfspaces_f64_dev (DEV below) reads the offset and
 // the window's first path row from a 16-byte state in device memory, so that a receding-horizon
 // loop can be replayed from one graph with a fresh draw per step (simulation/closed_loop.py);
@@ -34,12 +34,15 @@
 // problem's own predicted path; drcvar_sampled_halfspaces_f64_risk (RISK below) is the device-state
 // form whose risk parameters are each problem's own row of a table in device memory;
 // drcvar_sampled_halfspaces_f64_metric (METRIC below) is the risk-table form that also stores each
-// unit's halfspace under its problem's own metric.  The source is compiled four times: into the
-// engine library with the first two entries, with DRCVAR_LOOP_PRED_LIBRARY into a library of its
+// unit's halfspace under its problem's own metric; drcvar_sampled_halfspaces_f64_route (ROUTE
+// below) is the metric form whose ego path is each problem's own.  The source is compiled five
+// times: into the engine library with the first two entries, with DRCVAR_LOOP_PRED_LIBRARY into a library of its
 // own (include/drcvar_loop_pred.h) that holds the third and instantiates only the PRED kernels,
 // with DRCVAR_LOOP_RISK_LIBRARY into another (include/drcvar_loop_risk.h) that holds the fourth and
 // instantiates only the RISK kernels, and with DRCVAR_LOOP_METRIC_LIBRARY into a last one
-// (include/drcvar_loop_metric.h) that holds the fifth and instantiates only the METRIC kernels.
+// (include/drcvar_loop_metric.h) that holds the fifth and instantiates only the METRIC kernels,
+// and with DRCVAR_LOOP_ROUTE_LIBRARY as one of the two objects of the route library
+// (include/drcvar_loop_route.h), which holds the sixth and instantiates only the ROUTE kernels.
 //
 // The draw is the sampler's (drcvar_generator.inc) and the selection the stored form's
 // (drcvar_selection.inc); the direction alone differs on purpose, by one more Newton step of the
@@ -57,6 +60,9 @@
 #endif
 #ifdef DRCVAR_LOOP_RISK_LIBRARY
 #include "drcvar_loop_risk.h"
+#endif
+#ifdef DRCVAR_LOOP_ROUTE_LIBRARY
+#include "drcvar_loop_route.h"
 #endif
 #include "drcvar_loop_metric.h"  // every build: the METRIC form's constants (no code without it)
 
@@ -123,6 +129,7 @@ __device__ __forceinline__ void store_record_selected(double* rec, double* sel, 
 //   PRED     the device-state form with a predicted ego (below; implies DEV)
 //   RISK     the device-state form with a risk table (below; implies DEV, never with PRED)
 //   METRIC   the risk-table form with a metric per problem (below; implies RISK)
+//   ROUTE    the metric form with an ego path per problem (below; implies METRIC)
 // Blocks of 512 threads are held to 128 VGPRs (four waves per SIMD): two workgroups share a CU,
 // so one unit's draw (VALU) overlaps the other's selection (barriers, LDS, one ranking wave).
 //
@@ -178,6 +185,12 @@ __device__ __forceinline__ void store_record_selected(double* rec, double* sel, 
 // uniform load of a const __restrict__ argument beside the table row, before barrier 0, written
 // before the launch and never by it (`state`'s visibility argument); both storing exits (the
 // bad / unbounded return and the finish, which the noise-free step reaches too) store the row.
+//
+// The route form (ROUTE, drcvar_sampled_halfspaces_f64_route): the metric form, whose ego row is
+// its own problem's: ego + b ego_ps + r ego_st, with the b the risk-table branch already forms.
+// The address stays uniform over the workgroup, so the two coordinates are still scalar loads of a
+// const __restrict__ argument written before the launch; one scalar multiply-add is all the form
+// adds.  ego_ps = 0 is the metric form's address.
 // ---------------------------------------------------------------------------------------------
 constexpr int kMaxStates = 8;  // DRCVAR_MPC_MAX_STATES
 struct NoState {};
@@ -211,22 +224,35 @@ struct MetricState {  // RiskState and the two pointers of the metric form
   const int32_t* __restrict__ metric;  // [B]
   double* __restrict__ selected;       // [units, 4]
 };
+struct RouteState {  // MetricState and the ego path's stride from problem to problem
+  const drcvar_step_state* __restrict__ state;
+  int64_t path_last;
+  const RiskRow* __restrict__ table;
+  int64_t O, D;
+  const int32_t* __restrict__ metric;
+  double* __restrict__ selected;
+  int64_t ego_ps;  // in doubles
+};
 
 template <int BLOCK, int PP, int LOG_NB, bool ISO, bool DEV = false, bool PRED = false,
-          bool RISK = false, bool METRIC = false>
+          bool RISK = false, bool METRIC = false, bool ROUTE = false>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BLOCK >= 512 ? 4 : 1)))
 sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __restrict__ ego,
                          DrawArgs a, Params prm, double* __restrict__ out,
                          int32_t* __restrict__ status, double* __restrict__ samples_out,
                          std::conditional_t<
-                             METRIC, MetricState,
+                             ROUTE, RouteState,
                              std::conditional_t<
-                                 RISK, RiskState,
-                                 std::conditional_t<PRED, PredState,
-                                                    std::conditional_t<DEV, DevState, NoState>>>> dev) {
+                                 METRIC, MetricState,
+                                 std::conditional_t<
+                                     RISK, RiskState,
+                                     std::conditional_t<
+                                         PRED, PredState,
+                                         std::conditional_t<DEV, DevState, NoState>>>>> dev) {
   static_assert(DEV || !PRED, "the predicted-ego form is a device-state form");
   static_assert((DEV && !PRED) || !RISK, "the risk-table form is a device-state form without PRED");
   static_assert(RISK || !METRIC, "the metric form is a risk-table form");
+  static_assert(METRIC || !ROUTE, "the route form is a metric form");
   constexpr int NW = BLOCK / kWave;
   constexpr int NB = 1 << LOG_NB;
   constexpr int Q = 2 * PP;  // sample slots per thread: 2 j the pair's first, 2 j + 1 its second
@@ -248,10 +274,12 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
   const int64_t o = u / a.T, t = u - o * a.T;
   int64_t ud = u;  // the unit whose Philox counters are drawn
   [[maybe_unused]] int32_t code = 0;  // METRIC: the problem's metric
+  [[maybe_unused]] int64_t ego_first = 0;  // ROUTE: where the problem's ego path starts
   if constexpr (RISK) {
     const int64_t b = o / dev.O;
     prm = dev.table[b].p;
     if constexpr (METRIC) code = dev.metric[b];
+    if constexpr (ROUTE) ego_first = b * dev.ego_ps;
     ud = ((b % dev.D) * dev.O + (o - b * dev.O)) * a.T + t;
   }
   int64_t r = t;  // the unit's row of nominal[o] and of ego
@@ -289,6 +317,7 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
     }
   } else {
     const double* ep = ego + r * a.ego_st;
+    if constexpr (ROUTE) ep = ego + ego_first + r * a.ego_st;
     e0 = ep[0];
     e1 = ep[1];
   }
@@ -512,6 +541,7 @@ struct Launch {
   RiskState risk;  // the risk-table form's, likewise
   const int32_t* metric;  // the metric form's two pointers
   double* selected;
+  int64_t ego_ps;  // the route form's stride
 };
 
 template <int BLOCK, int PP, int LOG_NB, bool ISO>
@@ -537,6 +567,13 @@ void launch_form(const Launch& L) {
   hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true, false, true, true>),
                      grid, block, 0, L.stream, L.nominal, L.ego, L.a, L.prm, L.out, L.status,
                      nullptr, ms);
+#elif defined(DRCVAR_LOOP_ROUTE_LIBRARY)
+  // this library launches the route form alone (L.prm is not read: the rows are the table's)
+  const RouteState rs{L.state, L.path_last, L.risk.table, L.risk.O, L.risk.D,
+                      L.metric, L.selected, L.ego_ps};
+  hipLaunchKernelGGL(
+      (sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true, false, true, true, true>), grid,
+      block, 0, L.stream, L.nominal, L.ego, L.a, L.prm, L.out, L.status, nullptr, rs);
 #else
   if (L.state)
     hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true>), grid, block, 0,
@@ -563,7 +600,8 @@ void launch_plan(Launch L) {
 // of nominal and ego; stream_offset is unused, the kernel loads it).  `pred` non-null: the
 // predicted-ego form, which has no `ego`.  `risk` non-null: the risk-table form, whose five risk
 // scalars here are placeholders (its Params are the table's rows).  `metric_form`: the metric form,
-// a risk-table form with `metric` and `selected`.
+// a risk-table form with `metric` and `selected`; `ego_problem_stride` is read by the route
+// library's build alone.
 int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_steps, int64_t nom_so,
                        int64_t nom_st, int64_t unit_begin, int64_t unit_count, int64_t n_samples,
                        double l00, double l10, double l11, uint64_t seed, uint64_t stream_offset,
@@ -573,7 +611,8 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
                        double epsilon, double* out, int32_t* status, double* samples_out, int64_t su,
                        int64_t sn, void* stream, const PredState* pred = nullptr,
                        const RiskState* risk = nullptr, bool metric_form = false,
-                       const int32_t* metric = nullptr, double* selected = nullptr) {
+                       const int32_t* metric = nullptr, double* selected = nullptr,
+                       int64_t ego_problem_stride = 0) {
   if (n_obstacles < 0 || n_steps < 0 || n_samples < 0 || unit_begin < 0 || unit_count < 0)
     return DRCVAR_ERR_INVALID_ARGUMENT;
   if (dev && path_steps < 1) return DRCVAR_ERR_INVALID_ARGUMENT;
@@ -629,6 +668,7 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
   if (risk) L.risk = *risk;
   L.metric = metric;
   L.selected = selected;
+  L.ego_ps = ego_problem_stride;
   (void)hipGetLastError();  // clear stale errors from unrelated work
   switch (pick_plan(n_samples)) {
     case 0: launch_plan<64, 1, 7>(L); break;
@@ -758,6 +798,34 @@ extern "C" int drcvar_sampled_halfspaces_f64_metric(
                             unit_count, n_samples, l00, l10, l11, seed, 0, state, true, path_steps,
                             zero_first_step, ego_path, ego_stride, 0.0, 0.0, 1.0, 0.0, 0.0, out,
                             status, nullptr, 0, 0, stream, nullptr, &rs, true, metric, selected);
+}
+#elif defined(DRCVAR_LOOP_ROUTE_LIBRARY)
+extern "C" int drcvar_sampled_halfspaces_f64_route(
+    const double* nominal_path, int64_t n_obstacles, int64_t path_steps, int64_t nom_so,
+    int64_t nom_st, int64_t n_steps, int64_t unit_begin, int64_t unit_count, int64_t n_samples,
+    double l00, double l10, double l11, uint64_t seed, const drcvar_step_state* state,
+    int32_t zero_first_step, const double* ego_path, int64_t ego_stride,
+    int64_t ego_problem_stride, int64_t n_obstacles_per_problem, const void* table,
+    int64_t draw_period, const int32_t* metric, double* out, int32_t* status, double* selected,
+    void* stream) {
+  // the stride first, then the metric entry's checks in its order
+  if (ego_problem_stride < 0) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (ego_problem_stride > (int64_t{1} << 40)) return DRCVAR_ERR_UNSUPPORTED;
+  if (n_obstacles_per_problem < 1 || draw_period < 1) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (n_obstacles > 0 && n_obstacles % n_obstacles_per_problem != 0)
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  const bool launches = unit_count > 0 && n_samples > 0;
+  if (launches && (!table || reinterpret_cast<uintptr_t>(table) % 16 != 0))
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  RiskState rs{};
+  rs.table = static_cast<const RiskRow*>(table);
+  rs.O = n_obstacles_per_problem;
+  rs.D = draw_period;
+  return sampled_halfspaces(nominal_path, n_obstacles, n_steps, nom_so, nom_st, unit_begin,
+                            unit_count, n_samples, l00, l10, l11, seed, 0, state, true, path_steps,
+                            zero_first_step, ego_path, ego_stride, 0.0, 0.0, 1.0, 0.0, 0.0, out,
+                            status, nullptr, 0, 0, stream, nullptr, &rs, true, metric, selected,
+                            ego_problem_stride);
 }
 #else
 extern "C" int drcvar_sampled_launch_plan(int64_t n_samples, int32_t* threads,

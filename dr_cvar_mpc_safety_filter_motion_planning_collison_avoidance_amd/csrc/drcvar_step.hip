@@ -3,7 +3,10 @@
 // of n_problems problems advancing in lockstep (include/drcvar_loop.h,
 // drcvar_mpc_step_advance_batch_f64).  The source is compiled twice, same kernel: into the engine
 // library with the single entry, and with DRCVAR_LOOP_LIBRARY into the loop library with the batch
-// entry (the engine library's symbol list stays what it was).
+// entry (the engine library's symbol list stays what it was).  A third build, with
+// DRCVAR_LOOP_ROUTE_LIBRARY, is one of the two objects of the route library
+// (include/drcvar_loop_route.h): the batch entry whose reference paths are each problem's own
+// (drcvar_mpc_step_advance_batch_route_f64), and only that kernel.
 //
 // Reference: the caller's loop around MPCSafetyFilter.filter_trajectory, once per control step
 // (core/mpc_filter.py:40-178): apply the first input, remember the optimum on a solved call
@@ -25,8 +28,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "drcvar_loop.h"
+#ifdef DRCVAR_LOOP_ROUTE_LIBRARY
+#include "drcvar_loop_route.h"
+#endif
 #include "drcvar_mpc.h"
 
 namespace {
@@ -60,7 +67,18 @@ __device__ __forceinline__ int64_t path_row(int64_t base, int64_t k, int64_t las
   return r < 0 ? 0 : (r > last ? last : r);
 }
 
-__global__ void __launch_bounds__(kThreads) step_advance_kernel(StepArgs a) {
+// The route form (ROUTE, drcvar_mpc_step_advance_batch_route_f64): problem b's two reference paths
+// start b * stride doubles after problem 0's.  b = blockIdx.x is uniform over the workgroup, so
+// the offsets are scalar arithmetic beside the other slices'; without ROUTE the strides are an
+// empty struct and the body is the instructions it was.
+struct NoStrides {};
+struct RouteStrides {
+  int64_t x_ref, u_ref;  // in doubles
+};
+
+template <bool ROUTE>
+__global__ void __launch_bounds__(kThreads) step_advance_kernel(
+    StepArgs a, [[maybe_unused]] std::conditional_t<ROUTE, RouteStrides, NoStrides> rs) {
   const int e = threadIdx.x;
   const int H = a.H, nx = a.nx, nu = a.nu;
   const int n_u = H * nu, n_w = (H + 1) * nx;
@@ -79,6 +97,10 @@ __global__ void __launch_bounds__(kThreads) step_advance_kernel(StepArgs a) {
     a.last_u += b * n_u;
     a.have_last += b;
     a.state += b;
+    if constexpr (ROUTE) {
+      a.x_ref_path += b * rs.x_ref;
+      a.u_ref_path += b * rs.u_ref;
+    }
   }
   // ---- reads (before the barrier) ----------------------------------------------------------
   const int64_t s = a.state->step;
@@ -132,14 +154,16 @@ __global__ void __launch_bounds__(kThreads) step_advance_kernel(StepArgs a) {
   }
 }
 
-// the checks both entries share, then one launch of n_problems workgroups
+// the checks every entry shares, then one launch of n_problems workgroups (the strides are read by
+// the route library's build alone)
 int launch_step_advance(const drcvar_mpc_model* model, int64_t n_problems, const double* x_out,
                         const double* u_out, const double* info, const double* x_ref_path,
                         const double* u_ref_path, int64_t path_steps, const double* disturbance,
                         int64_t step_begin, int64_t log_rows, double* x_log, double* u_log,
                         double* info_log, double* x0, double* x_ref_win, double* u_fallback,
                         double* last_u, int32_t* have_last, drcvar_step_state* state,
-                        void* stream) {
+                        void* stream, [[maybe_unused]] int64_t x_ref_problem_stride = 0,
+                        [[maybe_unused]] int64_t u_ref_problem_stride = 0) {
   if (!model || !x_out || !u_out || !info || !x_ref_path || !u_ref_path || !x_log || !u_log ||
       !info_log || !x0 || !x_ref_win || !u_fallback || !last_u || !have_last || !state)
     return DRCVAR_ERR_INVALID_ARGUMENT;
@@ -150,6 +174,8 @@ int launch_step_advance(const drcvar_mpc_model* model, int64_t n_problems, const
       model->n_inputs > DRCVAR_MPC_MAX_INPUTS)
     return DRCVAR_ERR_INVALID_ARGUMENT;
   if (n_problems > INT32_MAX) return DRCVAR_ERR_UNSUPPORTED;  // one workgroup each: the grid's limit
+  if (x_ref_problem_stride > (int64_t{1} << 40) || u_ref_problem_stride > (int64_t{1} << 40))
+    return DRCVAR_ERR_UNSUPPORTED;  // (after every invalid argument: an invalid call stays invalid)
   StepArgs a{};
   a.x_out = x_out;
   a.u_out = u_out;
@@ -173,14 +199,36 @@ int launch_step_advance(const drcvar_mpc_model* model, int64_t n_problems, const
   a.nx = model->n_states;
   a.nu = model->n_inputs;
   (void)hipGetLastError();  // clear stale errors from unrelated work
-  hipLaunchKernelGGL(step_advance_kernel, dim3(static_cast<unsigned>(n_problems)), dim3(kThreads),
-                     0, static_cast<hipStream_t>(stream), a);
+#ifdef DRCVAR_LOOP_ROUTE_LIBRARY
+  hipLaunchKernelGGL(step_advance_kernel<true>, dim3(static_cast<unsigned>(n_problems)),
+                     dim3(kThreads), 0, static_cast<hipStream_t>(stream), a,
+                     RouteStrides{x_ref_problem_stride, u_ref_problem_stride});
+#else
+  hipLaunchKernelGGL(step_advance_kernel<false>, dim3(static_cast<unsigned>(n_problems)),
+                     dim3(kThreads), 0, static_cast<hipStream_t>(stream), a, NoStrides{});
+#endif
   return hipGetLastError() == hipSuccess ? DRCVAR_OK : DRCVAR_ERR_LAUNCH;
 }
 
 }  // namespace
 
-#ifndef DRCVAR_LOOP_LIBRARY
+#ifdef DRCVAR_LOOP_ROUTE_LIBRARY
+extern "C" int drcvar_mpc_step_advance_batch_route_f64(
+    const drcvar_mpc_model* model, int64_t n_problems, const double* x_out, const double* u_out,
+    const double* info, const double* x_ref_path, const double* u_ref_path, int64_t path_steps,
+    int64_t x_ref_problem_stride, int64_t u_ref_problem_stride, const double* disturbance,
+    int64_t step_begin, int64_t log_rows, double* x_log, double* u_log, double* info_log,
+    double* x0, double* x_ref_win, double* u_fallback, double* last_u, int32_t* have_last,
+    drcvar_step_state* state, void* stream) {
+  if (n_problems < 0) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (n_problems == 0) return DRCVAR_OK;  // nothing to do: no launch, no other argument is looked at
+  if (x_ref_problem_stride < 0 || u_ref_problem_stride < 0) return DRCVAR_ERR_INVALID_ARGUMENT;
+  return launch_step_advance(model, n_problems, x_out, u_out, info, x_ref_path, u_ref_path,
+                             path_steps, disturbance, step_begin, log_rows, x_log, u_log, info_log,
+                             x0, x_ref_win, u_fallback, last_u, have_last, state, stream,
+                             x_ref_problem_stride, u_ref_problem_stride);
+}
+#elif !defined(DRCVAR_LOOP_LIBRARY)
 extern "C" int drcvar_mpc_step_advance_f64(
     const drcvar_mpc_model* model, const double* x_out, const double* u_out, const double* info,
     const double* x_ref_path, const double* u_ref_path, int64_t path_steps,

@@ -312,8 +312,8 @@ def check_step_state(state, device: torch.device) -> None:
 
 
 def check_path(t, name: str, shape, device=None) -> None:
-    """A whole path of the device-state entries: a float64 tensor of ``shape`` (None = any size)
-    with a contiguous last dimension, on the GPU (``device``, when given).  Dtype and shape are
+    """A whole path of the device-state entries, 2-D or (obstacles or problems first) 3-D: a
+    float64 tensor of ``shape`` (None = any size) with a contiguous last dimension, on the GPU (``device``, when given).  Dtype and shape are
     checked before the device."""
     if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
         raise ValueError(f"{name} must be a float64 tensor")
@@ -559,10 +559,11 @@ class RiskTable:
 
 
 def _risk_launch_setup(nominal_path, ego_path, n_obstacles, n_steps, n_samples, params, state,
-                       draw_period, table, noise_cov, unit_begin, unit_count, out, status, chol):
-    """The checks and launch-uniform values that the risk-table and the metric launch share
-    (:func:`prepare_sampled_halfspaces_risk`): ``(dev, BO, P, O, B, D, T, n, u0, count, whole, out,
-    table, (l00, l10, l11))``."""
+                       draw_period, table, noise_cov, unit_begin, unit_count, out, status, chol,
+                       routes=False):
+    """The checks and launch-uniform values that the risk-table, the metric and the route launch
+    share (:func:`prepare_sampled_halfspaces_risk`): ``(dev, BO, P, O, B, D, T, n, u0, count, whole,
+    out, table, (l00, l10, l11))``.  ``routes``: ego_path is ``[B, P, 2]``, a path per problem."""
     if not isinstance(params, RiskTable):
         raise ValueError("params must be a RiskTable")
     params.validate()
@@ -580,7 +581,7 @@ def _risk_launch_setup(nominal_path, ego_path, n_obstacles, n_steps, n_samples, 
     D = B if draw_period is None else int(draw_period)
     if D < 1:
         raise ValueError(f"draw_period={draw_period} must be at least 1")
-    check_path(ego_path, "ego_path", (P, 2), dev)
+    check_path(ego_path, "ego_path", (B, P, 2) if routes else (P, 2), dev)
     check_step_state(state, dev)
     T, n = int(n_steps), int(n_samples)
     if T < 0:
@@ -697,7 +698,8 @@ def prepare_sampled_halfspaces_metric(nominal_path: torch.Tensor, ego_path: torc
                                       zero_first_step: bool = True, unit_begin: int = 0,
                                       unit_count: int | None = None, out: torch.Tensor | None = None,
                                       selected: torch.Tensor | None = None,
-                                      status: torch.Tensor | None = None, stream=None, chol=None
+                                      status: torch.Tensor | None = None, stream=None, chol=None,
+                                      _routes: bool = False
                                       ) -> tuple[PreparedLaunch, torch.Tensor, torch.Tensor]:
     """Freeze one ``drcvar_sampled_halfspaces_f64_metric`` call (``include/drcvar_loop_metric.h``):
     :func:`prepare_sampled_halfspaces_risk` whose launch also writes, for every unit, the halfspace
@@ -732,7 +734,7 @@ def prepare_sampled_halfspaces_metric(nominal_path: torch.Tensor, ego_path: torc
                 raise ValueError(f"selected must be a contiguous float64 {list(shape)} tensor")
     dev, BO, P, O, B, D, T, n, u0, count, whole, out, table, (l00, l10, l11) = _risk_launch_setup(
         nominal_path, ego_path, n_obstacles, n_steps, n_samples, params, state, draw_period, table,
-        noise_cov, unit_begin, unit_count, out, status, chol)
+        noise_cov, unit_begin, unit_count, out, status, chol, routes=_routes)
     if codes is None:
         codes = metric_codes(metric, B, dev)
     elif codes.device != dev:
@@ -742,17 +744,20 @@ def prepare_sampled_halfspaces_metric(nominal_path: torch.Tensor, ego_path: torc
                                dtype=torch.float64, device=dev)
     elif selected.device != dev:
         raise ValueError(f"selected must live on {dev}")
-    lib = _native.metric_lib()
+    # (the route launch: the same arguments, and the ego path's two strides in place of one)
+    ego_strides = (ego_path.stride(1), ego_path.stride(0)) if _routes else (ego_path.stride(0),)
+    entry = _native.route_lib().drcvar_sampled_halfspaces_f64_route if _routes else \
+        _native.metric_lib().drcvar_sampled_halfspaces_f64_metric
     args = (ctypes.c_void_p(nominal_path.data_ptr()), BO, P, nominal_path.stride(0),
             nominal_path.stride(1), T, u0, count, n, l00, l10, l11,
             ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), ctypes.c_void_p(state.data_ptr()),
             ctypes.c_int32(1 if zero_first_step else 0),
-            ctypes.c_void_p(ego_path.data_ptr()), ego_path.stride(0), O,
+            ctypes.c_void_p(ego_path.data_ptr()), *ego_strides, O,
             ctypes.c_void_p(table.data_ptr()), D, ctypes.c_void_p(codes.data_ptr()),
             ctypes.c_void_p(out.data_ptr()),
             ctypes.c_void_p(status.data_ptr() if status is not None else None),
             ctypes.c_void_p(selected.data_ptr()), ctypes.c_void_p(_stream_handle(dev, stream)))
-    launch = PreparedLaunch(lib.drcvar_sampled_halfspaces_f64_metric, args,
+    launch = PreparedLaunch(entry, args,
                             (nominal_path, ego_path, state, table, codes, out, status, selected))
     return launch, out, selected
 
@@ -763,6 +768,48 @@ def sampled_halfspaces_metric(nominal_path: torch.Tensor, ego_path: torch.Tensor
     """One ``drcvar_sampled_halfspaces_f64_metric`` launch (arguments:
     :func:`prepare_sampled_halfspaces_metric`): returns ``(out, selected)``."""
     launch, out, selected = prepare_sampled_halfspaces_metric(
+        nominal_path, ego_path, n_obstacles, n_steps, n_samples, params, metric, state, **kwargs)
+    if out.numel() > 0:
+        launch()
+    return out, selected
+
+
+def prepare_sampled_halfspaces_route(nominal_path: torch.Tensor, ego_path: torch.Tensor,
+                                     n_obstacles: int, n_steps: int, n_samples: int,
+                                     params: RiskTable, metric, state: torch.Tensor, **kwargs
+                                     ) -> tuple[PreparedLaunch, torch.Tensor, torch.Tensor]:
+    """Freeze one ``drcvar_sampled_halfspaces_f64_route`` call (``include/drcvar_loop_route.h``):
+    :func:`prepare_sampled_halfspaces_metric` with an ego path per problem.  Returns ``(launch,
+    out, selected)``.
+
+    ``ego_path`` is ``[B, P, 2]`` with adjacent coordinates and any problem and row strides (an
+    expanded path, problem stride 0, is the metric launch's one path); the ego of unit ``(b O + o)
+    T + t`` is ``ego_path[b, c(step + t)]``.  Per problem b, ``out``, ``status`` and ``selected``
+    hold byte for byte what :func:`prepare_sampled_halfspaces_metric` gives for the unit window
+    ``[b O T, (b + 1) O T)`` with ``ego_path[b]``.  Negative strides are a ``ValueError``.
+    Everything else, keyword arguments included: :func:`prepare_sampled_halfspaces_metric`."""
+    # what the host alone can tell about ego_path, before anything else: the shape the kernel
+    # would read through the raw pointer and the two strides
+    if not isinstance(ego_path, torch.Tensor) or ego_path.dtype != torch.float64 or \
+            ego_path.dim() != 3 or ego_path.shape[2] != 2 or ego_path.stride(2) != 1:
+        raise ValueError("ego_path must be a float64 [B, P, 2] tensor with adjacent coordinates")
+    if isinstance(nominal_path, torch.Tensor) and nominal_path.dim() == 3 and int(n_obstacles) >= 1 \
+            and nominal_path.shape[0] % int(n_obstacles) == 0:
+        want = (nominal_path.shape[0] // int(n_obstacles), nominal_path.shape[1], 2)
+        if tuple(ego_path.shape) != want:
+            raise ValueError(f"ego_path must have shape {list(want)}, got {tuple(ego_path.shape)}")
+    if ego_path.stride(0) < 0 or ego_path.stride(1) < 0:
+        raise ValueError("ego_path must not have negative strides")
+    return prepare_sampled_halfspaces_metric(nominal_path, ego_path, n_obstacles, n_steps, n_samples,
+                                             params, metric, state, _routes=True, **kwargs)
+
+
+def sampled_halfspaces_route(nominal_path: torch.Tensor, ego_path: torch.Tensor, n_obstacles: int,
+                             n_steps: int, n_samples: int, params: RiskTable, metric,
+                             state: torch.Tensor, **kwargs) -> tuple[torch.Tensor, torch.Tensor]:
+    """One ``drcvar_sampled_halfspaces_f64_route`` launch (arguments:
+    :func:`prepare_sampled_halfspaces_route`): returns ``(out, selected)``."""
+    launch, out, selected = prepare_sampled_halfspaces_route(
         nominal_path, ego_path, n_obstacles, n_steps, n_samples, params, metric, state, **kwargs)
     if out.numel() > 0:
         launch()

@@ -721,8 +721,8 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
 
     ``nominal_path`` is ``[B, O, P, 2]`` (one obstacle scenario per problem) or ``[O, P, 2]`` (the
     same in every problem); either way it is materialised once as a contiguous ``[B O, P, 2]``.
-    ``x_ref_path [P, nx]`` and ``u_ref_path [P, nu]`` are shared by all problems (the halfspace
-    launch has one ego path); ``disturbance`` is ``[B, D, nx]`` or None.  The other arguments are
+    ``x_ref_path [P, nx]`` and ``u_ref_path [P, nu]`` are shared by all problems, or per problem
+    (below); ``disturbance`` is ``[B, D, nx]`` or None.  The other arguments are
     :class:`RecedingHorizonFilter`'s.  One control step is
 
     1. one ``drcvar_sampled_halfspaces_f64_dev`` launch over the B O obstacles (``T = H``), writing
@@ -767,6 +767,21 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
     with ``linearize="predicted"`` is a ``ValueError``; with a string the batch is what it was,
     launch for launch.
 
+    ``x_ref_path`` may be ``[B, P, nx]`` and ``u_ref_path`` ``[B, P, nu]``: every loop then follows
+    its OWN route (``include/drcvar_loop_route.h``).  If either is 3-D both are
+    materialised as contiguous ``[B, P, .]`` and ``ego_path`` is ``[B, P, 2]``.  With
+    ``linearize="reference"`` step 1 is one ``drcvar_sampled_halfspaces_f64_route`` launch, the
+    metric launch whose unit takes its ego row from its own problem's path: a ``RiskParams`` is
+    taken as a table of B equal rows and a string metric as B equal codes, ``draw_period`` (None:
+    B) is allowed, and step 2 solves on ``engine.selected_views``.  With
+    ``linearize="predicted"`` step 1 stays the ``_pred`` launch, which reads no ego path.  Step 3
+    is ``drcvar_mpc_step_advance_batch_route_f64`` either way: workgroup b refills ``x_ref_win[b]``
+    and ``u_fallback[b]`` from problem b's paths.  ``reset`` and the ``reference`` backend gather
+    each problem's own windows (``engine.sampled_halfspaces`` per problem on that problem's ego
+    window; the advance in torch ops with a per-problem ``index_select``).  A 3-D path whose first
+    dimension is not B is a ``ValueError``; with 2-D paths the batch is what it was, launch for
+    launch, and the route library is not loaded.
+
     ``reset(x0)`` takes ``[B, nx]`` or ``[nx]``.  ``run(n, backend)`` returns ``(states [B, n + 1,
     nx], inputs [B, n, nu], info [B, n, 10])``; backends, log capacity, rebasing, the limit of D
     steps per reset under a disturbance and the treatment of failed solves (a logged step; nothing
@@ -785,6 +800,13 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
             raise ValueError(f"steps_per_graph={steps_per_graph} must be at least 1")
         check_evaluate(evaluate)
         check_linearize(linearize, relinearize)
+        # a route per problem: either reference path is [B, P, .]
+        routes = any(isinstance(t, torch.Tensor) and t.dim() == 3 for t in (x_ref_path, u_ref_path))
+        if routes and names is None and linearize == "reference":
+            # the route launch is a metric launch: B equal codes
+            if int(n_problems) < 1:
+                raise ValueError(f"n_problems={n_problems} must be at least 1")
+            names = (metric,) * int(n_problems)
         if names is not None and not isinstance(params, engine.RiskTable):
             # a metric per problem rides on the risk-table launch: B equal rows
             params.validate()
@@ -800,8 +822,13 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         H, nx, nu = model.horizon, model.nx, model.nu
         B = int(n_problems)
         O, P = check_batch_shapes(nominal_path, disturbance, B, nx)
-        engine.check_path(x_ref_path, "x_ref_path", (P, nx))
-        engine.check_path(u_ref_path, "u_ref_path", (P, nu))
+        paths = ((x_ref_path, "x_ref_path", nx), (u_ref_path, "u_ref_path", nu))
+        for t, name, _ in paths:   # (both, before either's device is looked at)
+            if isinstance(t, torch.Tensor) and t.dim() == 3 and t.shape[0] != B:
+                raise ValueError(f"{name} holds {t.shape[0]} problems, n_problems={B}")
+        for t, name, width in paths:
+            per_problem = isinstance(t, torch.Tensor) and t.dim() == 3
+            engine.check_path(t, name, (B, P, width) if per_problem else (P, width))
         for t, name in ((nominal_path, "nominal_path"), (x_ref_path, "x_ref_path"),
                         (u_ref_path, "u_ref_path"), (disturbance, "disturbance")):
             if t is not None and t.device != dev:
@@ -814,12 +841,19 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         self.max_iter, self.tol, self.polish, self.options = int(max_iter), float(tol), bool(polish), options
         self.steps_per_graph = int(steps_per_graph)
         self.nominal_path = nominal_path.expand(B, O, P, 2).reshape(B * O, P, 2).contiguous()
+        self.routes = routes
+        if routes:   # both paths [B, P, .], whichever was given per problem
+            x_ref_path, u_ref_path = x_ref_path.expand(B, P, nx), u_ref_path.expand(B, P, nu)
         self.x_ref_path = x_ref_path.contiguous()
         self.u_ref_path = u_ref_path.contiguous()
         self.disturbance = None if disturbance is None else disturbance.contiguous()
         self.path_steps = P
         C = torch.as_tensor(model.C).to(dev)
-        self.ego_path = (self.x_ref_path @ C.T).contiguous()   # formed once
+        if routes:   # [B, P, 2]: per problem the product the shared path takes, so equal routes
+            #          give the shared path's bits
+            self.ego_path = torch.stack([(xr @ C.T).contiguous() for xr in self.x_ref_path])
+        else:
+            self.ego_path = (self.x_ref_path @ C.T).contiguous()   # formed once
         f64 = dict(dtype=torch.float64, device=dev)
         # the fixed buffers every captured launch reads or writes
         self._state = torch.zeros((B, 2), dtype=torch.int64, device=dev)   # B x [stream_offset, step]
@@ -859,8 +893,9 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
 
     # ---- priming (torch ops, not a mode of the advance kernel) --------------------------------
     def _window(self, path, first, rows):
+        """``[rows, .]`` of a shared path, ``[B, rows, .]`` of per-problem paths."""
         idx = (self._rows[rows] + first).clamp_(0, self.path_steps - 1)
-        return path.index_select(0, idx)
+        return path.index_select(path.dim() - 2, idx)
 
     def _write_state(self):
         word = torch.tensor([_signed64(self._offset), self._step], dtype=torch.int64)
@@ -917,7 +952,9 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
             halfspaces = self._lin_launch(stream, 1)
             again = self._lin_launch(stream, 0) if self.relinearize else None
         elif self._codes is not None:
-            halfspaces, _, _ = engine.prepare_sampled_halfspaces_metric(
+            prepare = engine.prepare_sampled_halfspaces_route if self.routes else \
+                engine.prepare_sampled_halfspaces_metric
+            halfspaces, _, _ = prepare(
                 self.nominal_path, self.ego_path, self.n_obstacles, H, self.n_samples, self.params,
                 self.metrics, self._state[0], draw_period=self.draw_period, table=self._risk_table,
                 codes=self._codes, noise_cov=self.noise_cov, seed=self.seed,
@@ -941,11 +978,16 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         vp = ctypes.c_void_p
         x_log, u_log, info_log = self._logs
         dist = self.disturbance
-        advance = engine.PreparedLaunch(_native.loop_lib().drcvar_mpc_step_advance_batch_f64, (
+        if self.routes:   # each problem's own paths: their strides after path_steps
+            entry = _native.route_lib().drcvar_mpc_step_advance_batch_route_f64
+            strides = (self.x_ref_path.stride(0), self.u_ref_path.stride(0))
+        else:
+            entry, strides = _native.loop_lib().drcvar_mpc_step_advance_batch_f64, ()
+        advance = engine.PreparedLaunch(entry, (
             ctypes.pointer(m.model), self.n_problems, vp(self._x.data_ptr()), vp(self._u.data_ptr()),
             vp(self._info.data_ptr()), vp(self.x_ref_path.data_ptr()), vp(self.u_ref_path.data_ptr()),
-            self.path_steps, vp(dist.data_ptr() if dist is not None else None), self._step_begin,
-            self._cap, vp(x_log.data_ptr()), vp(u_log.data_ptr()), vp(info_log.data_ptr()),
+            self.path_steps, *strides, vp(dist.data_ptr() if dist is not None else None),
+            self._step_begin, self._cap, vp(x_log.data_ptr()), vp(u_log.data_ptr()), vp(info_log.data_ptr()),
             vp(self._x0.data_ptr()), vp(self._x_ref_win.data_ptr()), vp(self._u_fb.data_ptr()),
             vp(self._last_u.data_ptr()), vp(self._have_last.data_ptr()), vp(self._state.data_ptr()),
             vp(int(stream.cuda_stream))), (self, x_log, u_log, info_log))
@@ -984,7 +1026,8 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         """The record ``[B O, H, 8]`` of a RiskTable batch from the entry that predates the table:
         per problem one ``engine.sampled_halfspaces`` call with ``params.row(b)`` on a nominal
         tensor whose obstacle rows ``(b mod D) O .. + O`` are the problem's gathered window (the
-        rows before them are never read) and the unit window that starts there."""
+        rows before them are never read) and the unit window that starts there; ``ego_window`` is
+        ``[H, 2]``, or ``[B, H, 2]`` with a route per problem."""
         H, B, O, D = self.model.horizon, self.n_problems, self.n_obstacles, self.draw_period
         records = []
         for b in range(B):
@@ -992,7 +1035,8 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
             nominal = torch.zeros(((r + 1) * O, H, 2), dtype=torch.float64, device=window.device)
             nominal[r * O:].copy_(window[b * O:(b + 1) * O])
             records.append(engine.sampled_halfspaces(
-                nominal, ego_window, self.n_samples, self.params.row(b), noise_cov=self.noise_cov,
+                nominal, ego_window[b] if ego_window.dim() == 3 else ego_window, self.n_samples,
+                self.params.row(b), noise_cov=self.noise_cov,
                 chol=self.chol, seed=self.seed, stream_offset=self._offset,
                 zero_first_step=self.zero_first_step, unit_begin=r * O * H, unit_count=O * H))
         return torch.cat(records).view(B * O, H, engine.OUT_WIDTH)
@@ -1048,7 +1092,7 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         self._x0.copy_(x_next)
         self._x_ref_win.copy_(self._window(self.x_ref_path, s + 1, H + 1))
         plain = self._window(self.u_ref_path, s + 1, H)
-        shifted = torch.cat((self._last_u[:, 1:], plain[H - 1:].expand(B, 1, m.nu)), dim=1)
+        shifted = torch.cat((self._last_u[:, 1:], plain[..., H - 1:, :].expand(B, 1, m.nu)), dim=1)
         self._u_fb.copy_(torch.where(self._have_last.bool()[:, None, None], shifted, plain))
         self._step, self._offset = s + 1, (self._offset + 1) & _MASK64
         self._write_state()

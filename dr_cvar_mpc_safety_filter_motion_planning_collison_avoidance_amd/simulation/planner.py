@@ -51,3 +51,27 @@ class ReferenceTrajectoryPlanner:
             u_ref[t] = pinv_b @ (x_ref[t + 1] - self.A @ x_ref[t])
         return x_ref, u_ref, {"status": "OPTIMAL", "distance": distance,
                               "time_to_goal": time_to_goal, "n_steps": n_steps}
+
+    def straight_line_routes(self, starts, goals, velocities=1.5):
+        """(x_ref [B, H+1, nx], u_ref [B, H, nu]): one :meth:`straight_line_trajectory` per route,
+        stacked (the reference paths of a ``RecedingHorizonBatch`` with a route per problem).
+        ``starts`` and ``goals`` are ``[2]`` or ``[B, 2]`` and ``velocities`` a scalar or ``[B]``;
+        they broadcast against each other, and row b is bit for bit the single call on the b-th
+        triple."""
+        starts = np.asarray(starts, dtype=np.float64)
+        goals = np.asarray(goals, dtype=np.float64)
+        velocities = np.asarray(velocities, dtype=np.float64)
+        if starts.ndim not in (1, 2) or goals.ndim not in (1, 2) or velocities.ndim > 1 or \
+                starts.shape[-1] != 2 or goals.shape[-1] != 2:
+            raise ValueError("starts and goals must be [2] or [B, 2], velocities a scalar or [B]")
+        try:
+            B = np.broadcast_shapes(starts.shape[:-1], goals.shape[:-1], velocities.shape, (1,))[0]
+        except ValueError:
+            raise ValueError(f"starts {starts.shape}, goals {goals.shape} and velocities "
+                             f"{velocities.shape} do not broadcast to one batch") from None
+        starts = np.broadcast_to(starts, (B, 2))
+        goals = np.broadcast_to(goals, (B, 2))
+        velocities = np.broadcast_to(velocities, (B,))
+        routes = [self.straight_line_trajectory(starts[b], goals[b], float(velocities[b]))
+                  for b in range(B)]
+        return np.stack([r[0] for r in routes]), np.stack([r[1] for r in routes])
