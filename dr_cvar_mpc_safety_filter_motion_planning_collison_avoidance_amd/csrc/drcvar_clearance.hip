@@ -19,18 +19,22 @@
 //
 // Small M with a large O T grid leaves the device empty, so grid.y splits the step range.  With
 // more than one split the output is first filled with all-ones bytes, every split combines its
-// partial minimum by an unsigned 64-bit atomic min on the bit pattern of the non-negative d^2
-// (the order of non-negative doubles is the order of their bit patterns: exact, independent of
-// arrival order), and a finishing launch applies sqrt - R in place.  One split stores directly.
-// Both paths take the minimum of the same d^2 values and apply the same sqrt: the same bits.
+// partial minimum by an unsigned 64-bit atomic min on a key, the bit pattern of the non-negative
+// d^2 plus one (the order of non-negative doubles is the order of their bit patterns: exact,
+// independent of arrival order) or 0 for NaN, which so wins, and a finishing launch decodes the key
+// and applies sqrt - R in place.  One split stores directly.  Both paths take the minimum of the
+// same d^2 values and apply the same sqrt: the same bits.
+//
+// Non-finite positions follow IEEE 754 as the NumPy mirror of these formulas does (the contract is
+// in drcvar_sampling.h): a NaN d^2 makes its clearance NaN and its step count nothing.  v_min_f64
+// alone would drop it; max_high below carries it.
 //
 // The source is compiled twice.  Into the engine library: the kernel above behind
 // drcvar_min_clearance_f64[_ex].  With DRCVAR_LOOP_EVAL_LIBRARY into a library of its own
 // (include/drcvar_loop_eval.h): the device-state, batched, one-row form for receding-horizon
 // loops replayed from a graph (loop_clearance_kernel below).  Both draw with draw_noise and form
 // the obstacle point and d^2 by the same expressions.  (A shared inline helper for those four lines
-// changed the first kernel's instruction schedule; as written the engine unit's code is the
-// instruction stream it was before the second form existed.)
+// changed the first kernel's instruction schedule, so they are written out in both.)
 
 #include <hip/hip_runtime.h>
 
@@ -100,6 +104,17 @@ __device__ __forceinline__ double min_f64(double a, double b) {
   return r;
 }
 
+// v_min_f64 returns the other operand when one is a quiet NaN, so a NaN d^2 would drop out of
+// every minimum.  It is carried beside the minimum instead: an unsigned maximum of the high words
+// of the d^2 values (one v_max_u32 per trajectory and point).  A d^2 = fma(dx, dx, dy * dy) is
+// either >= +0 (high word at most that of +inf) or a NaN that the fma has quieted (high word, with
+// or without the sign, above kInfHigh): the maximum is above kInfHigh exactly when a member is NaN.
+constexpr uint32_t kInfHigh = 0x7ff00000u;
+__device__ __forceinline__ uint32_t max_high(uint32_t h, double d2) {
+  const uint32_t w = static_cast<uint32_t>(__double2hiint(d2));
+  return h > w ? h : w;
+}
+
 #ifndef DRCVAR_LOOP_EVAL_LIBRARY
 template <int K, bool kLaplace>
 __global__ __launch_bounds__(kBlock) void clearance_kernel(const double* __restrict__ ego,
@@ -118,16 +133,19 @@ __global__ __launch_bounds__(kBlock) void clearance_kernel(const double* __restr
   const int64_t t1 = t0 + a.steps_per_split < a.T ? t0 + a.steps_per_split : a.T;
   const double inf = std::numeric_limits<double>::infinity();
   double mn[K];
+  uint32_t nan_met = 0;  // bit k: some d^2 of trajectory k was NaN
 #pragma unroll
   for (int k = 0; k < K; ++k) mn[k] = inf;
   for (int64_t t = t0; t < t1; ++t) {
     double ex[K], ey[K], mo[K];
+    uint32_t ho[K];  // max_high over this step's d^2 of trajectory k
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const double* e = ego + k * a.ego_sk + t * a.ego_st;
       ex[k] = e[0];
       ey[k] = e[1];
       mo[k] = inf;
+      ho[k] = 0;
     }
     const bool noisy = !(a.zero_first && t == 0);  // the noise-free first step: no Philox call
     const double* nom = nominal + t * a.nom_st;
@@ -139,14 +157,19 @@ __global__ __launch_bounds__(kBlock) void clearance_kernel(const double* __restr
 #pragma unroll
       for (int k = 0; k < K; ++k) {
         const double dx = ex[k] - px, dy = ey[k] - py;
-        mo[k] = min_f64(mo[k], fma(dx, dx, dy * dy));
+        const double d2 = fma(dx, dx, dy * dy);
+        mo[k] = min_f64(mo[k], d2);
+        ho[k] = max_high(ho[k], d2);
       }
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       mn[k] = min_f64(mn[k], mo[k]);
+      nan_met |= static_cast<uint32_t>(ho[k] > kInfHigh) << k;
       if (hits) {
-        const unsigned long long hit = __builtin_amdgcn_ballot_w64(valid && mo[k] < a.RR);
+        // a minimum with a NaN member is NaN and counts nothing
+        const unsigned long long hit =
+            __builtin_amdgcn_ballot_w64(valid && mo[k] < a.RR && ho[k] <= kInfHigh);
         if (hit != 0 && (threadIdx.x & 63) == 0)
           atomicAdd(hits + k * a.T + t, static_cast<unsigned long long>(__builtin_popcountll(hit)));
       }
@@ -155,25 +178,31 @@ __global__ __launch_bounds__(kBlock) void clearance_kernel(const double* __restr
   if (!valid) return;
   if (gridDim.y == 1) {
 #pragma unroll
-    for (int k = 0; k < K; ++k) out[k * a.out_sk + i] = __builtin_sqrt(mn[k]) - a.R;
+    for (int k = 0; k < K; ++k)
+      out[k * a.out_sk + i] = (nan_met >> k & 1u) ? std::numeric_limits<double>::quiet_NaN()
+                                                  : __builtin_sqrt(mn[k]) - a.R;
   } else {
+    // key: 0 for NaN (it wins every atomic min), else the bit pattern of min d^2 >= +0 plus one
+    // (at most that of +inf plus one: below the all-ones fill)
 #pragma unroll
     for (int k = 0; k < K; ++k)
       atomicMin(reinterpret_cast<unsigned long long*>(out + k * a.out_sk + i),
-                static_cast<unsigned long long>(__double_as_longlong(mn[k])));
+                (nan_met >> k & 1u) ? 0ull
+                                    : static_cast<unsigned long long>(__double_as_longlong(mn[k])) + 1ull);
   }
 }
 
-// The split form's last pass: out[k, i] holds the bit pattern of min d^2 (all-ones where no split
-// wrote: the empty O T grid), replaced in place by sqrt - R.
+// The split form's last pass: out[k, i] holds the key of min d^2 (its bit pattern plus one; 0 where
+// a split met a NaN; all-ones where no split wrote: the empty O T grid), replaced in place by
+// sqrt - R, or by NaN.
 __global__ __launch_bounds__(kBlock) void clearance_finish_kernel(double* out, int64_t out_sk,
                                                                   int64_t M, double R) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (i >= M) return;
   double* p = out + blockIdx.y * out_sk + i;
-  const long long bits = __double_as_longlong(*p);
-  const double d2 = bits == -1LL ? std::numeric_limits<double>::infinity() : __longlong_as_double(bits);
-  *p = __builtin_sqrt(d2) - R;
+  const long long key = __double_as_longlong(*p);
+  const double d2 = key == -1LL ? std::numeric_limits<double>::infinity() : __longlong_as_double(key - 1);
+  *p = key == 0 ? std::numeric_limits<double>::quiet_NaN() : __builtin_sqrt(d2) - R;
 }
 
 template <bool kLaplace>
@@ -204,8 +233,8 @@ void launch_for_k(int K, dim3 grid, hipStream_t s, const double* ego, const doub
 // nominal row are uniform over the workgroup (scalar loads), and the table load is paid once per
 // workgroup: a thread takes per_thread realisations, kBlock apart (coalesced min_d2 rows), and
 // blockIdx.x picks the chunk of per_thread kBlock realisations.  Exactly one thread owns (b, m) in
-// a launch: the running minimum is a load, a v_min_f64 and a store, ordered against the previous
-// control step's launch by the stream alone.  The hit count of a wave is summed over its
+// a launch: the running minimum is a load, a v_min_f64 and a store (NaN kept: max_high above),
+// ordered against the previous control step's launch by the stream alone.  The hit count of a wave is summed over its
 // realisations in a scalar register (one ballot and popcount each) and leaves as at most one
 // integer atomic add.  Nothing depends on per_thread or the grid but which thread owns (b, m).
 constexpr int kMaxStates = 8;           // DRCVAR_MPC_MAX_STATES
@@ -278,6 +307,7 @@ __global__ __launch_bounds__(kBlock) void loop_clearance_kernel(
     // a lane past M draws realisation 0 (no index depends on it) and neither stores nor counts
     const uint64_t gm = static_cast<uint64_t>(valid ? m : 0) * static_cast<uint64_t>(a.OT);
     double mo = inf;
+    uint32_t ho = 0;  // max_high over this launch's d^2(m, o)
     const double* nom = nom_b;
     uint64_t ot = static_cast<uint64_t>(s);  // o T_n + s
     for (int64_t o = 0; o < a.O; ++o, nom += a.nom_so, ot += static_cast<uint64_t>(a.Tn)) {
@@ -285,10 +315,19 @@ __global__ __launch_bounds__(kBlock) void loop_clearance_kernel(
       if (noisy) draw_noise<kLaplace>(gm + ot, n, s_turn, s_log, &nx, &ny);
       const double px = nom[0] + nx, py = nom[1] + ny;
       const double dx = ex - px, dy = ey - py;
-      mo = min_f64(mo, fma(dx, dx, dy * dy));
+      const double d2 = fma(dx, dx, dy * dy);
+      mo = min_f64(mo, d2);
+      ho = max_high(ho, d2);
     }
-    if (valid) out[m] = min_f64(out[m], mo);
-    if (hits) count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(valid && mo < a.RR));
+    // a NaN met now is stored, a NaN stored by an earlier launch stays; this launch's count
+    // depends on this launch's d^2 alone
+    if (valid) {
+      const double prev = out[m];
+      out[m] = (ho > kInfHigh || prev != prev) ? std::numeric_limits<double>::quiet_NaN()
+                                               : min_f64(prev, mo);
+    }
+    if (hits)
+      count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(valid && mo < a.RR && ho <= kInfHigh));
   }
   if (hits && count != 0 && (threadIdx.x & 63) == 0)
     __hip_atomic_fetch_add(hits + b * (a.log_rows + 1) + static_cast<int64_t>(i),
@@ -311,7 +350,7 @@ extern "C" int drcvar_loop_clearance_f64_ex(
   if (n_problems < 0 || n_obstacles < 0 || n_realizations < 0 || noise_steps < 0 ||
       realizations_per_thread < 0 || (noise_kind != 0 && noise_kind != 1))
     return DRCVAR_ERR_INVALID_ARGUMENT;
-  if (!(p0 == p0) || !(p1 == p1) || !(p2 == p2) || !(combined_radius >= 0.0))
+  if (!std::isfinite(p0) || !std::isfinite(p1) || !std::isfinite(p2) || !(combined_radius >= 0.0))
     return DRCVAR_ERR_INVALID_ARGUMENT;
   if (noise_kind == 1 && (p0 < 0.0 || p1 < 0.0)) return DRCVAR_ERR_INVALID_ARGUMENT;
   if (n_states < 1 || n_states > kMaxStates || path_steps < 1 || log_rows < 0)
@@ -405,7 +444,7 @@ extern "C" int drcvar_min_clearance_f64_ex(const double* ego, int64_t n_traj, in
   if (n_traj < 0 || n_obstacles < 0 || n_steps < 0 || m_begin < 0 || n_realizations < 0 ||
       step_splits < 0 || (noise_kind != 0 && noise_kind != 1))
     return DRCVAR_ERR_INVALID_ARGUMENT;
-  if (!(p0 == p0) || !(p1 == p1) || !(p2 == p2) || !(combined_radius >= 0.0))
+  if (!std::isfinite(p0) || !std::isfinite(p1) || !std::isfinite(p2) || !(combined_radius >= 0.0))
     return DRCVAR_ERR_INVALID_ARGUMENT;
   if (noise_kind == 1 && (p0 < 0.0 || p1 < 0.0)) return DRCVAR_ERR_INVALID_ARGUMENT;
   constexpr int64_t kMaxUnits = int64_t{1} << 20, kMaxReal = int64_t{1} << 40;

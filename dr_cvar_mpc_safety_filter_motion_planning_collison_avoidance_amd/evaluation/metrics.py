@@ -6,7 +6,9 @@ Reference: ``collision_rate`` (:6-16), ``expectation_of_shortfall`` (:18-32), ``
 Every function takes a NumPy array (the reference's own NumPy calls, value for value) or a float64
 device tensor.  A device tensor is reduced on the device by torch ops — one sort serves the five
 quantiles, the minimum and the maximum; ``torch.quantile`` is not used, it refuses more than 16 M
-elements — and the results come back as Python floats in one copy.
+elements — and the results come back as Python floats in one copy.  Non-finite clearances give what
+the NumPy calls give: a NaN among them makes the minimum and every quantile NaN (the sort puts NaN
+last, so the sorted order alone would read past it), an all-+inf sample has the median +inf.
 """
 from __future__ import annotations
 
@@ -68,15 +70,25 @@ def _safety_metrics_device(d, threshold):
     if n == 0:
         raise ValueError("safety_metrics needs at least one clearance")
     s, _ = torch.sort(d)
-    vals = [d.mean(), s[0], s[-1], d.std(unbiased=False), (d < 0).to(torch.float64).mean(),
-            _shortfall_t(d, threshold)]
-    for _, q in _QUANTILES:
+    # the sort puts NaN last: s[-1] is NaN exactly when a clearance is.  NumPy's minimum and
+    # quantiles of such a sample are NaN; the sorted order alone would skip the NaN.
+    undefined = torch.isnan(s[-1])
+    nan = torch.full_like(s[-1], float("nan"))
+    vals = [d.mean(), torch.where(undefined, nan, s[0]), s[-1], d.std(unbiased=False),
+            (d < 0).to(torch.float64).mean(), _shortfall_t(d, threshold)]
+    for key, q in _QUANTILES:
         # np.percentile, method "linear": virtual index q/100 (n - 1), interpolated between its
         # neighbours in the sorted order
         pos = q / 100.0 * (n - 1)
         lo = min(int(np.floor(pos)), n - 1)
         hi = min(lo + 1, n - 1)
-        vals.append(torch.lerp(s[lo], s[hi], pos - lo))
+        v = torch.lerp(s[lo], s[hi], pos - lo)
+        if key == "median":
+            # np.median is the mean of the middle element(s), which infinite neighbours leave
+            # defined where the interpolation's difference does not (+inf: the empty obstacle grid)
+            a, b = s[lo], (s[lo] if pos == lo else s[hi])
+            v = torch.where(torch.isfinite(v), v, (a + b) / 2)
+        vals.append(torch.where(undefined, nan, v))
     host = torch.stack(vals).tolist()
     keys = ["mean", "min", "max", "std", "collision_rate", "expected_shortfall"] + [k for k, _ in _QUANTILES]
     return dict(zip(keys, host))

@@ -61,7 +61,8 @@ def min_clearance_device(ego, nominal, n_realizations, *, noise="laplace", noise
     only: a window of a longer run, a subset of the trajectories or another ``step_splits`` gives
     the same bits.  With ``step_hits=True`` also returns ``[K, T]`` int64, the number of
     realisations in collision at each step.  ``out`` may be any float64 ``[K, M]`` view with
-    adjacent realisations.
+    adjacent realisations.  Non-finite positions follow IEEE 754: ``out[k, m]`` is NaN exactly when
+    a squared distance entering it is NaN, and such a step counts nothing; nothing else changes.
     """
     _check_positions("ego", ego, "[K, T, 2]")
     _check_positions("nominal", nominal, "[O, T, 2]")

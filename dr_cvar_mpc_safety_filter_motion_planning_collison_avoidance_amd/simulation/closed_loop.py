@@ -264,27 +264,45 @@ class _Evaluated:
         leading problem dimension): ``min_clearance [B, M]`` = sqrt(min d^2) - R, ``collided [B]``
         the fraction of realisations in collision at some visited state, ``step_hits [B, rows]``
         and ``step_collision_rate`` for the states since the last rebase (row 0: the state the
-        logs start from), and ``metrics``, ``evaluation.metrics.safety_metrics`` per problem."""
+        logs start from), and ``metrics``, ``evaluation.metrics.safety_metrics`` per problem.  A
+        problem with a NaN clearance has ``collided`` NaN (:func:`safety_statistics`)."""
         if self.evaluate is None:
             raise RuntimeError("the loop was built without evaluate=")
         if not self._primed:
             raise RuntimeError("call reset(x0) before safety()")
         R = self.evaluate.combined_radius
-        f64 = dict(dtype=torch.float64, device=self.model.device)
         if self._eval_mode == "reference":
             clearance, hits = self._reference_safety()
-            collided = clearance < 0
+            result = safety_statistics(None, hits, R, clearance=clearance)
         else:
-            clearance = torch.sqrt(self._min_d2) - R
-            hits = self._eval_hits[:, :self._i + 1].clone()
-            collided = self._min_d2 < R * R
-        M = torch.full((), float(clearance.shape[1]), **f64)   # a tensor divisor (monte_carlo.py)
-        result = {"min_clearance": clearance, "collided": collided.sum(dim=1).to(torch.float64) / M,
-                  "step_hits": hits, "step_collision_rate": hits.to(torch.float64) / M,
-                  "metrics": [metrics.safety_metrics(row) for row in clearance]}
+            result = safety_statistics(self._min_d2, self._eval_hits[:, :self._i + 1].clone(), R)
         if not isinstance(self, RecedingHorizonBatch):
             result = {k: v[0] for k, v in result.items()}
         return result
+
+
+def safety_statistics(min_d2, hits, R, clearance=None):
+    """What ``safety()`` reports, from the evaluation's accumulators alone (tensors on any device):
+    ``min_d2 [B, M]`` the running minimum of the squared distance, ``hits [B, rows]`` the per-step
+    counts, ``R`` the combined radius.  ``clearance [B, M]`` given (the reference mode, which has
+    clearances and no squared distances): a realisation collided when its clearance is negative.
+
+    A NaN clearance (a non-finite position met the evaluation kernel, which propagates it) makes
+    problem b's sample undefined: ``collided[b]`` is NaN, as ``metrics`` are, never a rate over the
+    realisations that happen to be comparable.  Other problems are untouched."""
+    if clearance is None:
+        clearance = torch.sqrt(min_d2) - R
+        collided = min_d2 < R * R
+    else:
+        collided = clearance < 0
+    f64 = dict(dtype=torch.float64, device=clearance.device)
+    M = torch.full((), float(clearance.shape[1]), **f64)   # a tensor divisor (monte_carlo.py)
+    rate = collided.sum(dim=1).to(torch.float64) / M
+    undefined = torch.isnan(clearance).any(dim=1)
+    return {"min_clearance": clearance,
+            "collided": torch.where(undefined, torch.full_like(rate, float("nan")), rate),
+            "step_hits": hits, "step_collision_rate": hits.to(torch.float64) / M,
+            "metrics": [metrics.safety_metrics(row) for row in clearance]}
 
 
 def check_linearize(linearize, relinearize):

@@ -43,6 +43,15 @@ extern "C" {
  * (common random numbers across loops); 1: independent ones.  noise_kind, p0, p1, p2 and
  * combined_radius are drcvar_min_clearance_f64's.
  *
+ * Non-finite positions follow IEEE 754, as in drcvar_min_clearance_f64 (NaN propagates through
+ * every minimum; the running one included):
+ *   min_d2[b, m] becomes NaN at the first evaluated launch in which some d2(m, o) is NaN, and stays
+ *     NaN through every later launch (a NaN the caller stored stays as well).
+ *   The launch that met the NaN adds nothing to step_hits[b, i] for that m; every launch counts by
+ *     its own d2 alone, so later launches count that m again when their d2 are not NaN.
+ *   The other problems keep their bits.  d2 = +inf (one infinite coordinate) is an ordinary member
+ *     of the minimum; inf - inf is NaN.
+ *
  * The entry ACCUMULATES: the caller sets min_d2 to +inf and step_hits to 0 before the first launch.
  * Exactly one thread owns (b, m) in a launch and launches are ordered by the stream alone; the
  * result does not depend on the launch geometry.  The clearance is sqrt(min_d2) - combined_radius,
@@ -55,7 +64,8 @@ extern "C" {
  *   min_d2 [B, n_realizations]: row stride out_sb (doubles), adjacent realisations
  *   step_hits [B, log_rows + 1] int64, dense, or NULL      B = n_problems
  *
- * Host checks: a negative n_problems, n_obstacles, n_realizations or noise_steps, a NaN parameter,
+ * Host checks: a negative n_problems, n_obstacles, n_realizations or noise_steps, a p0, p1 or p2
+ * that is NaN or infinite (the noise itself must be finite), a NaN combined_radius,
  * a negative Laplace scale, combined_radius < 0, noise_kind outside {0, 1}, n_states outside 1..8,
  * path_steps < 1, log_rows < 0: DRCVAR_ERR_INVALID_ARGUMENT.  Then n_problems, n_realizations or
  * n_obstacles equal to 0: DRCVAR_OK, nothing is launched and no pointer is looked at.  Then a null

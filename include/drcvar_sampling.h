@@ -107,12 +107,27 @@ int drcvar_sample_units_f64(const double* nominal, int64_t n_obstacles, int64_t 
  * step_splits    (_ex) workgroup rows the step range is split over; 0 = chosen from the sizes.  The
  *                result does not depend on it, bit for bit.
  *
- * 1 <= n_traj <= 8, n_obstacles * n_steps <= 2^20, m_begin + n_realizations <= 2^40 (and at most
- * 2^39 realisations per call), otherwise DRCVAR_ERR_UNSUPPORTED.  A null pointer, a negative size,
- * a NaN parameter, a negative Laplace scale or a negative radius: DRCVAR_ERR_INVALID_ARGUMENT.
+ * 1 <= n_traj <= 8, n_obstacles * n_steps <= 2^20, m_begin + n_realizations <= 2^40 (m_begin = 2^40
+ * with n_realizations = 0 included) and n_realizations <= 2^39 - 256 per call (a workgroup takes 256
+ * realisations and the grid has at most 2^31 - 1 workgroups), otherwise DRCVAR_ERR_UNSUPPORTED.  A
+ * null pointer, a negative size, a negative Laplace scale, a negative radius, or a p0, p1 or p2 that
+ * is NaN or infinite (the noise itself must be finite): DRCVAR_ERR_INVALID_ARGUMENT.
  * n_realizations == 0: DRCVAR_OK, no kernel launched.  n_obstacles * n_steps == 0 with
- * n_realizations > 0: min_clearance is filled with +inf.  Non-finite positions give unspecified
- * clearances, never an out-of-range access (no index depends on data).
+ * n_realizations > 0: min_clearance is filled with +inf.
+ *
+ * Non-finite positions follow IEEE 754, as the NumPy restatement of these formulas does (NaN
+ * propagates through every minimum), and never cause an out-of-range access (no index depends on
+ * data):
+ *   min_clearance[k, m] is NaN exactly when some d2(k, m, o, t) of the call is NaN.  Every other
+ *     element has the bits it has without the NaN: a NaN in trajectory k changes nothing in the rows
+ *     k' != k, and a NaN in a nominal position makes NaN every clearance it enters.
+ *   step_hits[k, t] counts the m for which min over o of d2 < R * R; a minimum with a NaN member is
+ *     NaN and counts nothing.  The counts of the other steps are unchanged.
+ *   An infinite coordinate is not a NaN: d2 = +inf is an ordinary member of the minimum (it never
+ *     wins against a finite one and never counts as a hit); inf - inf, an ego and an obstacle
+ *     coordinate infinite with the same sign, is NaN.
+ * This holds for both noise kinds, at the noise-free step 0 as at the others, and for every
+ * step_splits.
  */
 int drcvar_min_clearance_f64(const double* ego, int64_t n_traj, int64_t ego_sk, int64_t ego_st,
                              const double* nominal, int64_t n_obstacles, int64_t n_steps,

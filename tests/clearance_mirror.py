@@ -5,6 +5,9 @@ tests/test_monte_carlo*.py, never the product path.
 One Philox4x32-10 call per (m, o, t): counter (g lo, g hi, stream lo, stream hi) with
 g = m (O T) + o T + t, key = seed.  Laplace: n = (bx (E(x0) - E(x1)), by (E(x2) - E(x3))),
 E(x) = -log u32(x).  Gaussian: (x0, x1) -> Box-Muller -> z, n = L z.
+
+Non-finite positions: ndarray.min propagates NaN, and that IEEE result is the kernel's contract
+(include/drcvar_sampling.h): a NaN d^2 makes its clearance NaN and its step count nothing.
 """
 import numpy as np
 

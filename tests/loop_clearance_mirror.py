@@ -1,7 +1,9 @@
 """NumPy restatement of drcvar_loop_clearance_f64 (include/drcvar_loop_eval.h), per problem and with
 the guards, built on tests/clearance_mirror.py: the noise a problem at path row s meets is
 ``clearance_mirror.noise(kind, params, O, T_n, M, seed, stream_offset)[:, :, s]``.  A helper of
-tests/test_loop_clearance_gpu.py, never the product path.
+tests/test_loop_clearance_gpu.py, never the product path.  np.minimum and ndarray.min propagate
+NaN: min_d2 takes a NaN d^2 and keeps it, and the launch that met it counts nothing for it, which
+is the entry's contract.
 """
 import numpy as np
 

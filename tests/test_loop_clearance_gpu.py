@@ -10,7 +10,10 @@ tests/test_monte_carlo_gpu.py derives for the same draws at distances <= 30 and 
 positions here lie in [-2, 2]), step_hits exactly (the mirror's margin |min_o d^2 - R^2| >= 1e-9 is
 asserted), the rows of problems left alone byte for byte, guard words around both outputs, the
 inputs unchanged; then bit for bit against the existing kernel (min_clearance_device, K = 1 per
-problem, far-padded rows), and across realisations-per-thread settings.
+problem, far-padded rows), and across realisations-per-thread settings.  Two further chains carry
+a NaN (a state at one launch; an obstacle's nominal row): the running minimum takes it and keeps it,
+that launch counts nothing for the realisations it touches, the other problems keep their bytes
+(include/drcvar_loop_eval.h).
 """
 import numpy as np
 import pytest
@@ -41,6 +44,15 @@ CASES = {
     "all_collide": (130, 3, 2, 4, 7, "laplace", 1, 7, True, True, (0, 10), 50.0),
     "none_collide": (130, 3, 2, 4, 7, "gaussian", 1, 7, False, True, (0, 10), 0.0),
 }
+# The chains with a NaN: (the case above they copy: the same shape, so script() seeds the same
+# inputs; the problem that meets the NaN; the launch at which it does; what is overwritten:
+# ("x0", state) at that launch only, or ("nominal", obstacle, path row), a whole row for all launches)
+POISON = {
+    "m65_wrap_nan_state": ("m65_wrap", 1, 2, ("x0", 3)),           # state nx - 1 is selected (ego x)
+    "m257_nan_nominal": ("m257", 1, 2, ("nominal", 2, 3)),         # problem 1 is at row 3 in launch 2
+}
+CLEAN = list(CASES)
+CASES.update({name: CASES[poison[0]] for name, poison in POISON.items()})
 
 
 @pytest.fixture(scope="module")
@@ -71,12 +83,19 @@ def script(name):
     x0[:, :, nx - 1] = rng.uniform(-2, 2, size=(LAUNCHES, B))
     x0[:, :, 0] = rng.uniform(-2, 2, size=(LAUNCHES, B))
     steps = np.array([[BASES[b] + r for b in range(B)] for r in range(LAUNCHES)], dtype=np.int64)
+    if name in POISON:
+        _, problem, launch_at, what = POISON[name]
+        if what[0] == "x0":
+            x0[launch_at, problem, what[1]] = np.nan
+        else:
+            nominal[problem * O + what[1], what[2]] = np.nan
     return c_out, nominal, x0, steps
 
 
-def mirror_chain(name):
+def mirror_chain(name, trace=None):
     """(min_d2 [B, M], step_hits [B, rows] or None, margin, log rows per launch and problem) of the
-    whole chain, from min_d2 = +inf and step_hits = 7."""
+    whole chain, from min_d2 = +inf and step_hits = 7.  ``trace``: a list that receives (min_d2,
+    step_hits) as they stand after each launch."""
     M, O, B, nx, Tn, noise, stride, offset, zero_first, with_hits, (begin, rows), R = CASES[name]
     c_out, nominal, x0, steps = script(name)
     min_d2 = np.full((B, M), np.inf)
@@ -89,12 +108,15 @@ def mirror_chain(name):
                          zero_first_step=zero_first)
         margin = min(margin, m)
         visited.append(i)
+        if trace is not None:
+            trace.append((min_d2.copy(), hits.copy() if with_hits else None))
     return min_d2, hits, margin, visited
 
 
-def device_chain(dev, name, per_thread=0):
+def device_chain(dev, name, per_thread=0, trace=None):
     """The chain on the device; returns (min_d2, step_hits) as NumPy arrays after checking the
-    guard words, the inputs, and after every launch the rows of the problems left alone."""
+    guard words, the inputs, and after every launch the rows of the problems left alone.
+    ``trace``: a list that receives (min_d2, step_hits) as NumPy arrays after each launch."""
     import torch
     M, O, B, nx, Tn, noise, stride, offset, zero_first, with_hits, (begin, rows), R = CASES[name]
     c_out, nominal, x0, steps = script(name)
@@ -123,16 +145,19 @@ def device_chain(dev, name, per_thread=0):
         before = (min_d2.clone(), hits.clone() if with_hits else None, x0_d.clone(), state.clone())
         launch()
         alone = [b for b in range(B) if visited[r][b] is None]
-        assert torch.equal(min_d2[alone], before[0][alone]), (r, alone)
+        assert torch.equal(min_d2[alone].view(torch.int64), before[0][alone].view(torch.int64)), (r, alone)
         if with_hits:
             assert torch.equal(hits[alone], before[1][alone]), (r, alone)
-        assert torch.equal(x0_d, before[2]) and torch.equal(state, before[3])
+        assert torch.equal(x0_d.view(torch.int64), before[2].view(torch.int64))   # (NaN included)
+        assert torch.equal(state, before[3])
+        if trace is not None:
+            trace.append((min_d2.cpu().numpy(), hits.cpu().numpy() if with_hits else None))
     out = out_base.cpu().numpy()
     guard = np.ones(out.shape, dtype=bool)
     guard[1:B + 1, :M] = False
     assert np.all(out[guard] == 123.0)
     assert hit_base[:2].tolist() == [-5, -5] and hit_base[-2:].tolist() == [-5, -5]
-    assert torch.equal(nom_d.cpu(), torch.from_numpy(nominal)) and bool(torch.all(nom_base[:, 0] == -7.0))
+    assert nom_d.cpu().numpy().tobytes() == nominal.tobytes() and bool(torch.all(nom_base[:, 0] == -7.0))
     return min_d2.cpu().numpy(), hits.cpu().numpy() if with_hits else None
 
 
@@ -140,13 +165,14 @@ def clearance(d2, R):
     return np.sqrt(d2) - R
 
 
-@pytest.mark.parametrize("name", list(CASES))
+@pytest.mark.parametrize("name", CLEAN)
 def test_chain_matches_mirror(dev, name):
     M, O, B = CASES[name][:3]
     R = CASES[name][-1]
     want, want_hits, margin, visited = mirror_chain(name)
     assert margin >= 1e-9
     got, hits = device_chain(dev, name)
+    assert np.array_equal(np.isnan(got), np.isnan(want)) and not np.isnan(want).any()
     assert np.array_equal(np.isinf(got), np.isinf(want))
     seen = np.isfinite(want)
     assert seen.any()
@@ -203,6 +229,50 @@ def test_geometry_independence(dev, name):
         got, hits = device_chain(dev, name, per_thread=per)
         assert got.tobytes() == base.tobytes(), per
         assert np.array_equal(hits, base_hits), per
+
+
+@pytest.mark.parametrize("per_thread", [0, 1, 3])
+@pytest.mark.parametrize("name", list(POISON))
+def test_nan_is_taken_kept_and_not_counted(dev, name, per_thread):
+    """After every launch of a chain with a NaN, against the mirror (np.minimum and ndarray.min
+    propagate NaN) and against the clean chain under the same geometry: the same elements are NaN
+    (the poisoned problem's row from the launch that meets the NaN to the end), the others agree
+    at atol 1e-13 in clearance, step_hits are the mirror's exactly (the poisoned launch adds
+    nothing; later launches count again), and the other problems' bytes are the clean chain's.
+    The margin is the clean case's: the NaN removes d^2 values from the mirror's set and adds
+    none."""
+    base, problem, launch_at, _ = POISON[name]
+    M, O, B = CASES[name][:3]
+    R = CASES[name][-1]
+    assert mirror_chain(base)[2] >= 1e-9
+    want, clean, got = [], [], []
+    with np.errstate(invalid="ignore"):
+        visited = mirror_chain(name, trace=want)[3]
+    assert all(row[problem] is not None for row in visited[launch_at:launch_at + 2])
+    device_chain(dev, base, per_thread, trace=clean)
+    device_chain(dev, name, per_thread, trace=got)
+    others = [b for b in range(B) if b != problem]
+    for r in range(LAUNCHES):
+        (w, wh), (c, ch), (g, gh) = want[r], clean[r], got[r]
+        poisoned = np.zeros((B, M), dtype=bool)
+        poisoned[problem] = r >= launch_at
+        assert np.array_equal(np.isnan(w), poisoned), r               # what the mirror says
+        assert np.array_equal(np.isnan(g), poisoned), r               # taken at launch_at, kept after
+        assert np.array_equal(np.isinf(g), np.isinf(w)), r
+        seen = np.isfinite(w)
+        if seen.any():
+            assert np.max(np.abs(clearance(g[seen], R) - clearance(w[seen], R))) <= 1e-13, r
+        np.testing.assert_array_equal(gh, wh, err_msg=f"launch {r}")
+        assert g[others].tobytes() == c[others].tobytes(), r
+        assert np.array_equal(gh[others], ch[others]), r
+        if r < launch_at:
+            assert g.tobytes() == c.tobytes() and np.array_equal(gh, ch), r
+    # the poisoned launch added nothing to its row of the counts; the clean chain did count there,
+    # and the launches after it count as in the clean chain
+    i = visited[launch_at][problem]
+    assert got[-1][1][problem, i] == 7 < clean[-1][1][problem, i]
+    later = [visited[r][problem] for r in range(launch_at + 1, LAUNCHES) if visited[r][problem] is not None]
+    assert later and all(got[-1][1][problem, j] == clean[-1][1][problem, j] for j in later)
 
 
 def test_stride_zero_shares_and_stride_one_separates(dev):

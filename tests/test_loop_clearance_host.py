@@ -66,6 +66,10 @@ def test_host_validation(ex):
     invalid = [dict(B=-1), dict(O=-1), dict(M=-1), dict(Tn=-1), dict(p0=nan), dict(p1=nan),
                dict(p2=nan), dict(R=nan), dict(R=-0.5), dict(kind=2), dict(kind=-1), dict(nx=0),
                dict(nx=9), dict(P=0), dict(P=-3), dict(log_rows=-1), dict(p0=-0.1), dict(p1=-0.1)]
+    # the noise itself must be finite, for both kinds
+    inf = float("inf")
+    invalid += [{name: v, "kind": kind} for name in ("p0", "p1", "p2") for v in (inf, -inf)
+                for kind in (0, 1)]
     for kw in invalid:
         assert _call(lib, ex, **kw) == INV, kw
         assert _call(lib, ex, B=0, **{k: v for k, v in kw.items() if k != "B"}) in (INV, OK)

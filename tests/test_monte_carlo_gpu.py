@@ -2,7 +2,9 @@
 evaluation/monte_carlo.py): the kernel against its NumPy mirror (tests/clearance_mirror.py) for both
 noise kinds, bitwise independence of the launch geometry, of the realisation window and of the
 number of trajectories, the distribution of the draws recovered from clearances alone, and
-run_monte_carlo_simulation against the host statistics and the host backend.
+run_monte_carlo_simulation against the host statistics and the host backend; the ragged step split,
+the Philox counter's carry between two lanes, the strict collision boundary, and non-finite
+positions, which follow IEEE 754 as the mirror does (include/drcvar_sampling.h).
 """
 import os
 
@@ -20,7 +22,8 @@ SEED, STREAM, FIRST = 2 ** 40 + 9, 2 ** 33 + 1, 2 ** 33      # the counter's hig
 LAPLACE_COV = np.diag([2 * 0.3 ** 2, 2 * 0.7 ** 2])           # scales (0.3, 0.7)
 GAUSS_COV = np.array([[0.25, 0.10], [0.10, 0.20]])            # L = (0.5, 0.2, 0.4)
 RADII = dict(robot_radius=0.55, obstacle_radius=0.45)          # R = 1
-SHAPES = [(1, 1, 1, 1), (1, 1, 2, 63), (3, 2, 5, 257), (8, 3, 4, 1000), (2, 1, 7, 4097)]
+SHAPES = [(1, 1, 1, 1), (1, 1, 2, 63), (3, 2, 5, 257), (8, 3, 4, 1000), (2, 1, 7, 4097),
+          (4, 2, 3, 65), (5, 1, 4, 64), (6, 2, 2, 129), (7, 3, 3, 256)]   # with these every K of 1..8
 
 
 @pytest.fixture(scope="module")
@@ -113,6 +116,182 @@ def test_geometry_window_and_trajectory_independence(dev, noise):
     other = mc.min_clearance_device(ego_d, nom_d, M, first_realization=FIRST, noise=noise,
                                     noise_cov=cov, seed=SEED + 1, stream_offset=STREAM, **RADII)
     assert not torch.equal(other, base)
+
+
+@pytest.mark.parametrize("noise", ["laplace", "gaussian"])
+def test_ragged_step_splits(dev, noise):
+    """T = 7: 3, 4 and 5 splits leave a last split of one step (and the host's "none empty"
+    recomputation turns 4 into 4 of 2, 2, 2, 1 and 5 into 4 as well), 2 leaves 4 + 3, 8 and 100
+    clamp to T.  Every one gives the automatic launch's bits."""
+    import torch
+    K, O, T, M = 3, 2, 7, 300
+    ego, nominal = case_inputs((K, O, T, M))
+    ego_d, nom_d = torch.from_numpy(ego).to(dev), torch.from_numpy(nominal).to(dev)
+    cov = LAPLACE_COV if noise == "laplace" else GAUSS_COV
+    kw = dict(noise=noise, noise_cov=cov, seed=SEED, stream_offset=STREAM, first_realization=FIRST,
+              step_hits=True, **RADII)
+    base, base_hits = mc.min_clearance_device(ego_d, nom_d, M, **kw)
+    assert 0 < int(base_hits.sum()) < K * T * M and bool(torch.isfinite(base).all())
+    for splits in (1, 2, 3, 4, 5, 7, 8, 100):
+        got, hits = mc.min_clearance_device(ego_d, nom_d, M, step_splits=splits, **kw)
+        assert torch.equal(got, base), splits
+        assert torch.equal(hits, base_hits), splits
+
+
+@pytest.mark.parametrize("noise", ["laplace", "gaussian"])
+def test_counter_carry_between_lanes(dev, noise):
+    """g = m O T + o T + t with O T = 6 and m from 2^32 // 6 - 150: the counter's low word wraps
+    and its high word steps from 0 to 1 inside realisation index 150 (2^32 = 6 (first + 150) + 4),
+    so lanes 0..149, lane 150 and lanes 151.. of one launch differ in how they see the high word
+    (with FIRST = 2^33 it is the same in every lane of a launch)."""
+    import torch
+    K, O, T, M = 3, 2, 3, 300
+    first = 2 ** 32 // 6 - 150
+    assert first == 715827732 and (first + 150) * 6 < 2 ** 32 <= (first + 150) * 6 + 5
+    ego, nominal = case_inputs((K, O, T, M))
+    nz = cm.noise(noise, mirror_params(noise), O, T, M, SEED, STREAM, first, True)
+    want, want_hits, margin = cm.min_clearance(ego, nominal, nz, RADII["robot_radius"] + RADII["obstacle_radius"])
+    assert margin >= 1e-9
+    ego_d, nom_d = torch.from_numpy(ego).to(dev), torch.from_numpy(nominal).to(dev)
+    cov = LAPLACE_COV if noise == "laplace" else GAUSS_COV
+    kw = dict(noise=noise, noise_cov=cov, seed=SEED, stream_offset=STREAM, step_hits=True, **RADII)
+    got, hits = mc.min_clearance_device(ego_d, nom_d, M, first_realization=first, **kw)
+    err = np.max(np.abs(got.cpu().numpy() - want))
+    print(f"carry {noise}: max |kernel - mirror| = {err:.3e}, margin {margin:.2e}")
+    assert err <= 1e-13
+    np.testing.assert_array_equal(hits.cpu().numpy(), want_hits)
+    lo, lo_hits = mc.min_clearance_device(ego_d, nom_d, 150, first_realization=first, **kw)
+    hi, hi_hits = mc.min_clearance_device(ego_d, nom_d, 150, first_realization=first + 150, **kw)
+    assert torch.equal(torch.cat((lo, hi), dim=1), got)
+    assert torch.equal(lo_hits + hi_hits, hits)
+
+
+@pytest.mark.parametrize("noise", ["laplace", "gaussian"])
+def test_collision_boundary_is_strict(dev, noise):
+    """d^2 on R^2 itself: T = 1 with zero_first_step (no Philox call, no noise), one obstacle at
+    the origin, R = 2.75 + 2.25 = 5, egos (3, 4), (3, 4 - ulp) and (3, 4 + ulp): d^2 = 25 exactly
+    (not a hit: the comparison is strict), just below (a hit in all 70 realisations) and just
+    above.  The margin condition of the other tests (no min_o d^2 within 1e-9 of R^2) is
+    deliberately not applied: it exists because a draw differs from the mirror's by rounding, and
+    here there is no draw; 3 - 0, y - 0, y y and 9 + y y are the same IEEE operations on both
+    sides, exact up to one shared rounding (the kernel's fma(dx, dx, dy dy) rounds 9 + round(y y)
+    once, as the mirror's sum does, 9 being exact)."""
+    import torch
+    M, R = 70, 5.0
+    ego = np.array([[[3.0, 4.0]], [[3.0, np.nextafter(4.0, 0.0)]], [[3.0, np.nextafter(4.0, 5.0)]]])
+    nominal = np.zeros((1, 1, 2))
+    nz = cm.noise(noise, mirror_params(noise), 1, 1, M, SEED, STREAM, FIRST, True)
+    assert not nz.any()
+    want, want_hits, _ = cm.min_clearance(ego, nominal, nz, R)
+    np.testing.assert_array_equal(want_hits, [[0], [M], [0]])
+    # (the clearance of the ego just inside is sqrt(25 - 4 ulp) - 5 = 0.0 after rounding: only the
+    # comparison of the squares tells it from the ego on the boundary)
+    assert want[0, 0] == 0.0 and want[1, 0] == 0.0 and want[2, 0] > 0.0
+    cov = LAPLACE_COV if noise == "laplace" else GAUSS_COV
+    for splits in (0, 1):
+        got, hits = mc.min_clearance_device(
+            torch.from_numpy(ego).to(dev), torch.from_numpy(nominal).to(dev), M, noise=noise,
+            noise_cov=cov, seed=SEED, stream_offset=STREAM, first_realization=FIRST,
+            zero_first_step=True, step_hits=True, step_splits=splits, robot_radius=2.75,
+            obstacle_radius=2.25)
+        assert hits.cpu().numpy().tolist() == [[0], [M], [0]]
+        assert got.cpu().numpy().tobytes() == want.tobytes()
+
+
+NAN, INF = float("nan"), float("inf")
+# name: (array, index, value) written into the clean inputs of shape (3, 2, 4, 70)
+NON_FINITE = {
+    "ego_one_coordinate": ("ego", (1, 2, 0), NAN),
+    "ego_whole_trajectory": ("ego", (1, slice(None), slice(None)), NAN),
+    "nominal_one_coordinate": ("nominal", (0, 3, 1), NAN),
+    "ego_step_infinite": ("ego", (0, 1, slice(None)), INF),       # d^2 = +inf: no NaN anywhere
+    "ego_noise_free_step": ("ego", (2, 0, 1), NAN),               # step 0: no draw under zero_first
+}
+NON_FINITE_SHAPE = (3, 2, 4, 70)
+_non_finite_cache = {}
+
+
+def non_finite_reference(noise, zero_first, name):
+    """(ego, nominal, mirror clearance, mirror hits, clean mirror clearance, clean mirror hits) of a
+    NON_FINITE case; the margin condition is asserted on every d^2 minimum that is not NaN."""
+    key = (noise, zero_first, name)
+    if key not in _non_finite_cache:
+        K, O, T, M = NON_FINITE_SHAPE
+        R = RADII["robot_radius"] + RADII["obstacle_radius"]
+        if (noise, zero_first) not in _non_finite_cache:
+            nz = cm.noise(noise, mirror_params(noise), O, T, M, SEED, STREAM, FIRST, zero_first)
+            ego, nominal = case_inputs(NON_FINITE_SHAPE)
+            clean = cm.min_clearance(ego, nominal, nz, R)
+            assert clean[2] >= 1e-9 and np.isfinite(clean[0]).all()
+            _non_finite_cache[(noise, zero_first)] = (nz, clean)
+        nz, clean = _non_finite_cache[(noise, zero_first)]
+        ego, nominal = case_inputs(NON_FINITE_SHAPE)
+        which, index, value = NON_FINITE[name]
+        (ego if which == "ego" else nominal)[index] = value
+        with np.errstate(invalid="ignore"):
+            d2 = cm.step_min_d2(ego, nominal, nz)
+            want, want_hits, _ = cm.min_clearance(ego, nominal, nz, R)
+            assert np.min(np.abs(d2[~np.isnan(d2)] - R * R)) >= 1e-9
+        _non_finite_cache[key] = (ego, nominal, want, want_hits, clean[0], clean[1])
+    return _non_finite_cache[key]
+
+
+@pytest.mark.parametrize("name", list(NON_FINITE))
+@pytest.mark.parametrize("zero_first", [True, False])
+@pytest.mark.parametrize("noise", ["laplace", "gaussian"])
+def test_non_finite_positions_follow_the_mirror(dev, noise, zero_first, name):
+    """A NaN d^2 makes its clearance NaN and counts nothing; everything else keeps its bits; an
+    infinite coordinate gives d^2 = +inf, which is no NaN (include/drcvar_sampling.h).  The direct
+    store (1 split) and the split form's keys (2 and 4 splits; with 4 every split holds one step,
+    so a NaN split meets finite splits in the atomic min)."""
+    import torch
+    K, O, T, M = NON_FINITE_SHAPE
+    ego, nominal, want, want_hits, clean, clean_hits = non_finite_reference(noise, zero_first, name)
+    nan_rows = np.isnan(want).any(axis=1)
+    if name == "ego_step_infinite":
+        assert not nan_rows.any() and np.isfinite(want).all()
+    elif name == "nominal_one_coordinate":
+        assert np.isnan(want).all() and not want_hits[:, 3].any()
+        np.testing.assert_array_equal(np.delete(want_hits, 3, axis=1), np.delete(clean_hits, 3, axis=1))
+    else:
+        k = 2 if name == "ego_noise_free_step" else 1
+        assert nan_rows.tolist() == [j == k for j in range(K)] and np.isnan(want[k]).all()
+    untouched = [k for k in range(K) if np.array_equal(want[k], clean[k])
+                 and np.array_equal(want_hits[k], clean_hits[k])]
+    assert len(untouched) == (0 if name == "nominal_one_coordinate" else K - 1)
+    cov = LAPLACE_COV if noise == "laplace" else GAUSS_COV
+    kw = dict(noise=noise, noise_cov=cov, seed=SEED, stream_offset=STREAM, first_realization=FIRST,
+              zero_first_step=zero_first, step_hits=True, **RADII)
+    ego_clean, nom_clean = case_inputs(NON_FINITE_SHAPE)
+    for splits in (1, 2, 4):
+        base, base_hits = mc.min_clearance_device(torch.from_numpy(ego_clean).to(dev),
+                                                  torch.from_numpy(nom_clean).to(dev), M,
+                                                  step_splits=splits, **kw)
+        got, hits = mc.min_clearance_device(torch.from_numpy(ego).to(dev),
+                                            torch.from_numpy(nominal).to(dev), M,
+                                            step_splits=splits, **kw)
+        g = got.cpu().numpy()
+        np.testing.assert_array_equal(np.isnan(g), np.isnan(want), err_msg=f"splits {splits}")
+        seen = ~np.isnan(want)
+        if seen.any():
+            assert np.max(np.abs(g[seen] - want[seen])) <= 1e-13, splits
+        np.testing.assert_array_equal(hits.cpu().numpy(), want_hits, err_msg=f"splits {splits}")
+        assert torch.equal(got[untouched], base[untouched]), splits
+        assert torch.equal(hits[untouched], base_hits[untouched]), splits
+
+
+def test_infinite_noise_parameter_is_rejected(dev):
+    """The noise itself must be finite: an infinite scale is DRCVAR_ERR_INVALID_ARGUMENT, as a NaN
+    one is, through the wrapper's return-code check; nothing is launched."""
+    import torch
+    from dr_cvar_mpc_safety_filter_motion_planning_collison_avoidance_amd import _native
+    ego = torch.zeros((2, 4, 2), dtype=torch.float64, device=dev)
+    nom = torch.zeros((3, 4, 2), dtype=torch.float64, device=dev)
+    for bad in (INF, NAN):
+        for cov in (np.diag([bad, 0.02]), np.diag([0.02, bad])):
+            with pytest.raises(_native.EngineError) as info:
+                mc.min_clearance_device(ego, nom, 5, noise="laplace", noise_cov=cov, **RADII)
+            assert info.value.code == _native.ERR_INVALID_ARGUMENT
 
 
 def test_empty_grids(dev):
