@@ -3,8 +3,9 @@
 bound with ctypes; beside it the loop library (``drcvar_loop.h``, :func:`loop_lib`), the
 loop-evaluation library (``drcvar_loop_eval.h``, :func:`eval_lib`), the predicted-ego library
 (``drcvar_loop_pred.h``, :func:`pred_lib`), the risk-table library (``drcvar_loop_risk.h``,
-:func:`risk_lib`), the metric library (``drcvar_loop_metric.h``, :func:`metric_lib`) and the route
-library (``drcvar_loop_route.h``, :func:`route_lib`), one entry family each.
+:func:`risk_lib`), the metric library (``drcvar_loop_metric.h``, :func:`metric_lib`), the route
+library (``drcvar_loop_route.h``, :func:`route_lib`) and the noise library
+(``drcvar_loop_noise.h``, :func:`noise_lib`), one entry family each.
 
 There is deliberately no fallback: if the shared library is missing or cannot be loaded every
 entry point raises :class:`NativeLibraryError`.  ``build()`` compiles it for gfx950 in-tree.
@@ -73,6 +74,14 @@ ROUTE_HEADER = os.path.join(INCLUDE_DIR, "drcvar_loop_route.h")
 ROUTE_UNIT = ((os.path.join(PKG_DIR, "csrc", "drcvar_sampled.hip"), ("-DDRCVAR_LOOP_ROUTE_LIBRARY",)),
               (os.path.join(PKG_DIR, "csrc", "drcvar_step.hip"), ("-DDRCVAR_LOOP_ROUTE_LIBRARY",)))
 ROUTE_SYMBOLS = ("drcvar_sampled_halfspaces_f64_route", "drcvar_mpc_step_advance_batch_route_f64")
+# The noise library (include/drcvar_loop_noise.h), by the metric library's recipe:
+# csrc/drcvar_sampled.hip compiled a sixth time, with DRCVAR_LOOP_NOISE_LIBRARY (7 kernels: the seven
+# plans of the noise form, whose isotropic form is a row's flag; none of the other libraries').
+NOISE_LIB_PATH = os.path.join(LIB_DIR, "libdrcvar_loop_noise.so")
+NOISE_HEADER = os.path.join(INCLUDE_DIR, "drcvar_loop_noise.h")
+NOISE_UNIT = (os.path.join(PKG_DIR, "csrc", "drcvar_sampled.hip"), ("-DDRCVAR_LOOP_NOISE_LIBRARY",))
+NOISE_SYMBOLS = ("drcvar_noise_table_row_bytes", "drcvar_noise_table_fill",
+                 "drcvar_sampled_halfspaces_f64_noise")
 
 ABI_VERSION = 3
 OUT_WIDTH = 8
@@ -300,12 +309,12 @@ def build(verbose: bool = False, extra_flags=()) -> str:
     import glob
     incs = sorted(glob.glob(os.path.join(PKG_DIR, "csrc", "*.inc")))  # tables the sources include
     headers = b"".join(open(h, "rb").read() for h in HEADERS + [LOOP_HEADER, EVAL_HEADER, PRED_HEADER, RISK_HEADER,
-                                                                   METRIC_HEADER, ROUTE_HEADER] + incs)
+                                                                   METRIC_HEADER, ROUTE_HEADER, NOISE_HEADER] + incs)
     # the compiler's identity is part of every key: objects of an older hipcc / ROCm are rebuilt
     toolchain = _toolchain(probe=True)
     objs, procs = [], []
     for src, defs in _compile_units() + [LOOP_UNIT, EVAL_UNIT, PRED_UNIT, RISK_UNIT, METRIC_UNIT,
-                                         *ROUTE_UNIT]:
+                                         *ROUTE_UNIT, NOISE_UNIT]:
         flags = _unit_flags(defs, extra_flags)
         key = hashlib.sha256(open(src, "rb").read() + headers + toolchain
                              + " ".join(flags).encode()).hexdigest()[:16]
@@ -324,11 +333,11 @@ def build(verbose: bool = False, extra_flags=()) -> str:
     for _, obj, _ in procs:
         os.replace(obj + ".tmp", obj)
     # (LOOP_UNIT, EVAL_UNIT, PRED_UNIT, RISK_UNIT and METRIC_UNIT come after the engine's objects,
-    # each a library of its own; ROUTE_UNIT's two objects are the last two, one library)
-    for path, members in ((LIB_PATH, objs[:-7]), (LOOP_LIB_PATH, objs[-7:-6]),
-                          (EVAL_LIB_PATH, objs[-6:-5]), (PRED_LIB_PATH, objs[-5:-4]),
-                          (RISK_LIB_PATH, objs[-4:-3]), (METRIC_LIB_PATH, objs[-3:-2]),
-                          (ROUTE_LIB_PATH, objs[-2:])):
+    # each a library of its own; ROUTE_UNIT's two objects are one library; NOISE_UNIT's is the last)
+    for path, members in ((LIB_PATH, objs[:-8]), (LOOP_LIB_PATH, objs[-8:-7]),
+                          (EVAL_LIB_PATH, objs[-7:-6]), (PRED_LIB_PATH, objs[-6:-5]),
+                          (RISK_LIB_PATH, objs[-5:-4]), (METRIC_LIB_PATH, objs[-4:-3]),
+                          (ROUTE_LIB_PATH, objs[-3:-1]), (NOISE_LIB_PATH, objs[-1:])):
         link = ["hipcc", f"--offload-arch={OFFLOAD_ARCH}", "-shared", "-fPIC", *members,
                 "-o", path + ".tmp"]
         if verbose:
@@ -656,6 +665,39 @@ def route_lib():
             handle.drcvar_mpc_step_advance_batch_route_f64.restype = ctypes.c_int
             _route_lib = handle
     return _route_lib
+
+
+_noise_lib = None
+
+
+def noise_lib():
+    """The loaded noise library (``include/drcvar_loop_noise.h``; raises NativeLibraryError if it
+    is not built: there is no fallback).  It shares the engine library's structs and return codes
+    and reads the rows the risk-table library fills, beside its own noise table."""
+    global _noise_lib
+    if _noise_lib is not None:
+        return _noise_lib
+    with _lock:
+        if _noise_lib is None:
+            if not os.path.exists(NOISE_LIB_PATH):
+                raise NativeLibraryError(
+                    f"noise library not built: {NOISE_LIB_PATH} is missing (run "
+                    f"__graft_entry__.build())")
+            try:
+                handle = ctypes.CDLL(NOISE_LIB_PATH)
+            except OSError as exc:  # pragma: no cover - depends on the ROCm install
+                raise NativeLibraryError(f"cannot load {NOISE_LIB_PATH}: {exc}") from exc
+            i64, i32, u64, ptr = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p
+            handle.drcvar_noise_table_row_bytes.argtypes = []
+            handle.drcvar_noise_table_row_bytes.restype = i64
+            handle.drcvar_noise_table_fill.argtypes = [ptr, i64, ptr, i64]
+            handle.drcvar_noise_table_fill.restype = ctypes.c_int
+            handle.drcvar_sampled_halfspaces_f64_noise.argtypes = [
+                ptr, i64, i64, i64, i64, i64, i64, i64, i64, ptr, i64, u64, ptr, i32,
+                ptr, i64, i64, i64, ptr, i64, ptr, ptr, ptr, ptr, ptr]
+            handle.drcvar_sampled_halfspaces_f64_noise.restype = ctypes.c_int
+            _noise_lib = handle
+    return _noise_lib
 
 
 def check(code: int) -> None:

@@ -26,7 +26,7 @@
 //
 // samples_out (optional): the kernel also stores the samples it drew; the record is the same bits.
 //
-// Six entries, one kernel template: drcvar_sampled_halfspaces_f64 freezes the stream offset and
+// Seven entries, one kernel template: drcvar_sampled_halfspaces_f64 freezes the stream offset and
 // the window in its arguments; drcvar_sampled_halfspaces_f64_dev (DEV below) reads the offset and
 // the window's first path row from a 16-byte state in device memory, so that a receding-horizon
 // loop can be replayed from one graph with a fresh draw per step (simulation/closed_loop.py);
@@ -35,14 +35,17 @@
 // form whose risk parameters are each problem's own row of a table in device memory;
 // drcvar_sampled_halfspaces_f64_metric (METRIC below) is the risk-table form that also stores each
 // unit's halfspace under its problem's own metric; drcvar_sampled_halfspaces_f64_route (ROUTE
-// below) is the metric form whose ego path is each problem's own.  The source is compiled five
-// times: into the engine library with the first two entries, with DRCVAR_LOOP_PRED_LIBRARY into a library of its
+// below) is the metric form whose ego path is each problem's own;
+// drcvar_sampled_halfspaces_f64_noise (NOISE below) is the route form whose noise factor is each
+// unit's own row of a table in device memory.  The source is compiled six times: into the engine library with the first two entries, with DRCVAR_LOOP_PRED_LIBRARY into a library of its
 // own (include/drcvar_loop_pred.h) that holds the third and instantiates only the PRED kernels,
 // with DRCVAR_LOOP_RISK_LIBRARY into another (include/drcvar_loop_risk.h) that holds the fourth and
 // instantiates only the RISK kernels, and with DRCVAR_LOOP_METRIC_LIBRARY into a last one
 // (include/drcvar_loop_metric.h) that holds the fifth and instantiates only the METRIC kernels,
 // and with DRCVAR_LOOP_ROUTE_LIBRARY as one of the two objects of the route library
-// (include/drcvar_loop_route.h), which holds the sixth and instantiates only the ROUTE kernels.
+// (include/drcvar_loop_route.h), which holds the sixth and instantiates only the ROUTE kernels,
+// and with DRCVAR_LOOP_NOISE_LIBRARY into the noise library (include/drcvar_loop_noise.h), which
+// holds the seventh and instantiates only the NOISE kernels.
 //
 // The draw is the sampler's (drcvar_generator.inc) and the selection the stored form's
 // (drcvar_selection.inc); the direction alone differs on purpose, by one more Newton step of the
@@ -63,6 +66,9 @@
 #endif
 #ifdef DRCVAR_LOOP_ROUTE_LIBRARY
 #include "drcvar_loop_route.h"
+#endif
+#ifdef DRCVAR_LOOP_NOISE_LIBRARY
+#include "drcvar_loop_noise.h"
 #endif
 #include "drcvar_loop_metric.h"  // every build: the METRIC form's constants (no code without it)
 
@@ -130,6 +136,7 @@ __device__ __forceinline__ void store_record_selected(double* rec, double* sel, 
 //   RISK     the device-state form with a risk table (below; implies DEV, never with PRED)
 //   METRIC   the risk-table form with a metric per problem (below; implies RISK)
 //   ROUTE    the metric form with an ego path per problem (below; implies METRIC)
+//   NOISE    the route form with a noise factor per unit (below; implies ROUTE; ISO is unused)
 // Blocks of 512 threads are held to 128 VGPRs (four waves per SIMD): two workgroups share a CU,
 // so one unit's draw (VALU) overlaps the other's selection (barriers, LDS, one ranking wave).
 //
@@ -191,6 +198,21 @@ __device__ __forceinline__ void store_record_selected(double* rec, double* sel, 
 // The address stays uniform over the workgroup, so the two coordinates are still scalar loads of a
 // const __restrict__ argument written before the launch; one scalar multiply-add is all the form
 // adds.  ego_ps = 0 is the metric form's address.
+//
+// The noise form (NOISE, drcvar_sampled_halfspaces_f64_noise): the route form, whose Cholesky
+// factor, isotropic flag and LogScale are row (o mod NP) T + t of `noise` in device memory instead
+// of the launch-uniform a.l00, a.l10, a.l11 and a.lg: the assumed covariance differs from obstacle
+// to obstacle and from window step to window step inside one launch.  A row is what the host of
+// the route entry would have passed for that factor (drcvar_noise_table_fill: the same isotropic
+// test, make_log_scale), so per unit the launch is the route form with that row's scalars.  The
+// row's address is uniform over the workgroup and the factor entered only in workgroup-uniform
+// places (draw_pair's operands, the LDS log table's lam, the window's s0, s1): the row is a
+// uniform load of a const __restrict__ argument (scalar memory), before barrier 0 beside the risk
+// row and the metric code, written before the launch and never by it: the visibility argument is
+// `state`'s.  The LogScale reaches fma_sc and fma_vs in the SGPRs it was loaded into.  Which of
+// draw_pair's two forms a unit takes is the row's flag, one uniform branch per Philox call; the
+// template's ISO is not read (the library instantiates ISO = false alone).  The host checks
+// NP <= n_obstacles; the caller keeps NP T rows readable.
 // ---------------------------------------------------------------------------------------------
 constexpr int kMaxStates = 8;  // DRCVAR_MPC_MAX_STATES
 struct NoState {};
@@ -233,26 +255,45 @@ struct RouteState {  // MetricState and the ego path's stride from problem to pr
   double* __restrict__ selected;
   int64_t ego_ps;  // in doubles
 };
+struct alignas(16) NoiseRow {  // one row of the noise table: a factor as the host would pass it
+  double l00, l10, l11;
+  int64_t iso;  // 1: the isotropic LogScale form (lg carries l00^2), 0: the general form (lg of 1)
+  LogScale lg;
+};
+struct NoiseState {  // RouteState and the noise table
+  const drcvar_step_state* __restrict__ state;
+  int64_t path_last;
+  const RiskRow* __restrict__ table;
+  int64_t O, D;
+  const int32_t* __restrict__ metric;
+  double* __restrict__ selected;
+  int64_t ego_ps;
+  const NoiseRow* __restrict__ noise;  // [NP T]
+  int64_t NP;                          // the noise period, in obstacles
+};
 
 template <int BLOCK, int PP, int LOG_NB, bool ISO, bool DEV = false, bool PRED = false,
-          bool RISK = false, bool METRIC = false, bool ROUTE = false>
+          bool RISK = false, bool METRIC = false, bool ROUTE = false, bool NOISE = false>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BLOCK >= 512 ? 4 : 1)))
 sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __restrict__ ego,
                          DrawArgs a, Params prm, double* __restrict__ out,
                          int32_t* __restrict__ status, double* __restrict__ samples_out,
                          std::conditional_t<
-                             ROUTE, RouteState,
+                             NOISE, NoiseState,
                              std::conditional_t<
-                                 METRIC, MetricState,
+                                 ROUTE, RouteState,
                                  std::conditional_t<
-                                     RISK, RiskState,
+                                     METRIC, MetricState,
                                      std::conditional_t<
-                                         PRED, PredState,
-                                         std::conditional_t<DEV, DevState, NoState>>>>> dev) {
+                                         RISK, RiskState,
+                                         std::conditional_t<
+                                             PRED, PredState,
+                                             std::conditional_t<DEV, DevState, NoState>>>>>> dev) {
   static_assert(DEV || !PRED, "the predicted-ego form is a device-state form");
   static_assert((DEV && !PRED) || !RISK, "the risk-table form is a device-state form without PRED");
   static_assert(RISK || !METRIC, "the metric form is a risk-table form");
   static_assert(METRIC || !ROUTE, "the route form is a metric form");
+  static_assert(ROUTE || !NOISE, "the noise form is a route form");
   constexpr int NW = BLOCK / kWave;
   constexpr int NB = 1 << LOG_NB;
   constexpr int Q = 2 * PP;  // sample slots per thread: 2 j the pair's first, 2 j + 1 its second
@@ -281,6 +322,15 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
     if constexpr (METRIC) code = dev.metric[b];
     if constexpr (ROUTE) ego_first = b * dev.ego_ps;
     ud = ((b % dev.D) * dev.O + (o - b * dev.O)) * a.T + t;
+  }
+  [[maybe_unused]] bool iso = ISO;  // NOISE: the row's flag
+  if constexpr (NOISE) {
+    const NoiseRow& nr = dev.noise[(o % dev.NP) * a.T + t];
+    a.l00 = nr.l00;
+    a.l10 = nr.l10;
+    a.l11 = nr.l11;
+    a.lg = nr.lg;
+    iso = nr.iso != 0;
   }
   int64_t r = t;  // the unit's row of nominal[o] and of ego
   if constexpr (DEV) {
@@ -343,9 +393,19 @@ sampled_halfspace_kernel(const double* __restrict__ nominal, const double* __res
     y[2 * j] = y[2 * j + 1] = ny;
     // a whole wave past the unit's pairs skips the call; idle lanes of a partly filled wave make
     // it on a counter of their own and drop the result
-    if (noisy && wave_first + j * BLOCK < pairs)
-      draw_pair<ISO>(g0 + static_cast<uint64_t>(j * BLOCK), a, nx, ny, s_turn, s_log, &x[2 * j],
-                     &y[2 * j], &x[2 * j + 1], &y[2 * j + 1]);
+    if (noisy && wave_first + j * BLOCK < pairs) {
+      if constexpr (NOISE) {  // the row's form: uniform over the workgroup
+        if (iso)
+          draw_pair<true>(g0 + static_cast<uint64_t>(j * BLOCK), a, nx, ny, s_turn, s_log,
+                          &x[2 * j], &y[2 * j], &x[2 * j + 1], &y[2 * j + 1]);
+        else
+          draw_pair<false>(g0 + static_cast<uint64_t>(j * BLOCK), a, nx, ny, s_turn, s_log,
+                           &x[2 * j], &y[2 * j], &x[2 * j + 1], &y[2 * j + 1]);
+      } else {
+        draw_pair<ISO>(g0 + static_cast<uint64_t>(j * BLOCK), a, nx, ny, s_turn, s_log, &x[2 * j],
+                       &y[2 * j], &x[2 * j + 1], &y[2 * j + 1]);
+      }
+    }
   }
   if (samples_out) {  // unit row `row`, sample i at + i sn, coordinates adjacent
     double* dst = samples_out + row * a.su;
@@ -542,6 +602,8 @@ struct Launch {
   const int32_t* metric;  // the metric form's two pointers
   double* selected;
   int64_t ego_ps;  // the route form's stride
+  const NoiseRow* noise;  // the noise form's table and period
+  int64_t noise_period;
 };
 
 template <int BLOCK, int PP, int LOG_NB, bool ISO>
@@ -574,6 +636,15 @@ void launch_form(const Launch& L) {
   hipLaunchKernelGGL(
       (sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true, false, true, true, true>), grid,
       block, 0, L.stream, L.nominal, L.ego, L.a, L.prm, L.out, L.status, nullptr, rs);
+#elif defined(DRCVAR_LOOP_NOISE_LIBRARY)
+  // this library launches the noise form alone (L.prm and L.a's factor are not read: the rows are
+  // the tables')
+  static_assert(!ISO, "the noise form reads the row's flag");
+  const NoiseState ns{L.state, L.path_last, L.risk.table, L.risk.O, L.risk.D, L.metric,
+                      L.selected, L.ego_ps, L.noise, L.noise_period};
+  hipLaunchKernelGGL(
+      (sampled_halfspace_kernel<BLOCK, PP, LOG_NB, false, true, false, true, true, true, true>),
+      grid, block, 0, L.stream, L.nominal, L.ego, L.a, L.prm, L.out, L.status, nullptr, ns);
 #else
   if (L.state)
     hipLaunchKernelGGL((sampled_halfspace_kernel<BLOCK, PP, LOG_NB, ISO, true>), grid, block, 0,
@@ -589,10 +660,23 @@ void launch_form(const Launch& L) {
 template <int BLOCK, int PP, int LOG_NB>
 void launch_plan(Launch L) {
   L.prm.hist_scale = static_cast<double>(1 << LOG_NB) / (2.0 * L.prm.window_sd);
+#ifdef DRCVAR_LOOP_NOISE_LIBRARY
+  launch_form<BLOCK, PP, LOG_NB, false>(L);  // one kernel per plan: the form is each row's flag
+#else
   if (L.iso)
     launch_form<BLOCK, PP, LOG_NB, true>(L);
   else
     launch_form<BLOCK, PP, LOG_NB, false>(L);
+#endif
+}
+
+// The sampler's test for its isotropic form (launch_samples): the draws are the same bits only if
+// this kernel takes that form exactly when the sampler does.  One expression for the launch-uniform
+// factor of every entry and for the rows of the noise table.
+inline bool isotropic_factor(double l00, double l10, double l11) {
+  const double lam = l00 * l00;
+  return l10 == 0.0 && l00 == l11 && l00 > 0.0 && std::isfinite(l00) && lam >= 0x1.0p-200 &&
+         lam <= 0x1.0p200;
 }
 
 // Every entry: the host checks, the launch-uniform arguments and the plan's launch.  `state`
@@ -601,7 +685,8 @@ void launch_plan(Launch L) {
 // predicted-ego form, which has no `ego`.  `risk` non-null: the risk-table form, whose five risk
 // scalars here are placeholders (its Params are the table's rows).  `metric_form`: the metric form,
 // a risk-table form with `metric` and `selected`; `ego_problem_stride` is read by the route
-// library's build alone.
+// library's build alone; `noise` and `noise_period` by the noise library's, whose l00, l10, l11 here
+// are placeholders (its factors are the noise table's rows).
 int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_steps, int64_t nom_so,
                        int64_t nom_st, int64_t unit_begin, int64_t unit_count, int64_t n_samples,
                        double l00, double l10, double l11, uint64_t seed, uint64_t stream_offset,
@@ -612,7 +697,8 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
                        int64_t sn, void* stream, const PredState* pred = nullptr,
                        const RiskState* risk = nullptr, bool metric_form = false,
                        const int32_t* metric = nullptr, double* selected = nullptr,
-                       int64_t ego_problem_stride = 0) {
+                       int64_t ego_problem_stride = 0, const void* noise = nullptr,
+                       int64_t noise_period = 1) {
   if (n_obstacles < 0 || n_steps < 0 || n_samples < 0 || unit_begin < 0 || unit_count < 0)
     return DRCVAR_ERR_INVALID_ARGUMENT;
   if (dev && path_steps < 1) return DRCVAR_ERR_INVALID_ARGUMENT;
@@ -650,12 +736,8 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
   L.a.pu = make_philox_uniform(static_cast<uint32_t>(stream_offset),
                                static_cast<uint32_t>(stream_offset >> 32),
                                static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
-  // the sampler's test for its isotropic form (launch_samples): the draws are the same bits only
-  // if this kernel takes that form exactly when the sampler does
-  const double lam = l00 * l00;
-  L.iso = l10 == 0.0 && l00 == l11 && l00 > 0.0 && std::isfinite(l00) && lam >= 0x1.0p-200 &&
-          lam <= 0x1.0p200;
-  L.a.lg = make_log_scale(L.iso ? lam : 1.0);
+  L.iso = isotropic_factor(l00, l10, l11);
+  L.a.lg = make_log_scale(L.iso ? l00 * l00 : 1.0);
   L.prm = make_params(robot_radius, obstacle_radius, alpha, delta, epsilon, n_samples);
   L.out = out;
   L.status = status;
@@ -669,6 +751,8 @@ int sampled_halfspaces(const double* nominal, int64_t n_obstacles, int64_t n_ste
   L.metric = metric;
   L.selected = selected;
   L.ego_ps = ego_problem_stride;
+  L.noise = static_cast<const NoiseRow*>(noise);
+  L.noise_period = noise_period;
   (void)hipGetLastError();  // clear stale errors from unrelated work
   switch (pick_plan(n_samples)) {
     case 0: launch_plan<64, 1, 7>(L); break;
@@ -826,6 +910,65 @@ extern "C" int drcvar_sampled_halfspaces_f64_route(
                             zero_first_step, ego_path, ego_stride, 0.0, 0.0, 1.0, 0.0, 0.0, out,
                             status, nullptr, 0, 0, stream, nullptr, &rs, true, metric, selected,
                             ego_problem_stride);
+}
+#elif defined(DRCVAR_LOOP_NOISE_LIBRARY)
+static_assert(sizeof(NoiseRow) % 16 == 0, "a noise row is a multiple of 16 bytes");
+
+extern "C" int64_t drcvar_noise_table_row_bytes(void) { return static_cast<int64_t>(sizeof(NoiseRow)); }
+
+extern "C" int drcvar_noise_table_fill(const double* chol, int64_t rows, void* out,
+                                       int64_t out_bytes) {
+  if (rows < 0 || out_bytes < 0) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (rows == 0) return DRCVAR_OK;
+  if (!chol || !out) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (rows > out_bytes / static_cast<int64_t>(sizeof(NoiseRow))) return DRCVAR_ERR_INVALID_ARGUMENT;
+  for (int64_t r = 0; r < 3 * rows; ++r)  // every row first: a rejected row writes nothing
+    if (!(chol[r] == chol[r])) return DRCVAR_ERR_INVALID_ARGUMENT;
+  for (int64_t r = 0; r < rows; ++r) {
+    NoiseRow row;
+    std::memset(&row, 0, sizeof(row));  // equal factors give equal bytes
+    row.l00 = chol[3 * r];
+    row.l10 = chol[3 * r + 1];
+    row.l11 = chol[3 * r + 2];
+    const bool iso = isotropic_factor(row.l00, row.l10, row.l11);
+    row.iso = iso ? 1 : 0;
+    row.lg = make_log_scale(iso ? row.l00 * row.l00 : 1.0);  // as sampled_halfspaces sets a.lg
+    std::memcpy(static_cast<char*>(out) + r * sizeof(NoiseRow), &row, sizeof(row));
+  }
+  return DRCVAR_OK;
+}
+
+extern "C" int drcvar_sampled_halfspaces_f64_noise(
+    const double* nominal_path, int64_t n_obstacles, int64_t path_steps, int64_t nom_so,
+    int64_t nom_st, int64_t n_steps, int64_t unit_begin, int64_t unit_count, int64_t n_samples,
+    const void* noise, int64_t noise_period, uint64_t seed, const drcvar_step_state* state,
+    int32_t zero_first_step, const double* ego_path, int64_t ego_stride,
+    int64_t ego_problem_stride, int64_t n_obstacles_per_problem, const void* table,
+    int64_t draw_period, const int32_t* metric, double* out, int32_t* status, double* selected,
+    void* stream) {
+  // the noise table first (row (o mod noise_period) T + t stays inside noise_period T rows for
+  // every o), then the route entry's checks in its order
+  if (noise_period < 1 || noise_period > n_obstacles) return DRCVAR_ERR_INVALID_ARGUMENT;
+  const bool launches = unit_count > 0 && n_samples > 0;
+  if (launches && (!noise || reinterpret_cast<uintptr_t>(noise) % 16 != 0))
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (ego_problem_stride < 0) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (ego_problem_stride > (int64_t{1} << 40)) return DRCVAR_ERR_UNSUPPORTED;
+  if (n_obstacles_per_problem < 1 || draw_period < 1) return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (n_obstacles > 0 && n_obstacles % n_obstacles_per_problem != 0)
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  if (launches && (!table || reinterpret_cast<uintptr_t>(table) % 16 != 0))
+    return DRCVAR_ERR_INVALID_ARGUMENT;
+  RiskState rs{};
+  rs.table = static_cast<const RiskRow*>(table);
+  rs.O = n_obstacles_per_problem;
+  rs.D = draw_period;
+  // (a placeholder factor that the NaN check accepts: the kernel reads the noise table's rows)
+  return sampled_halfspaces(nominal_path, n_obstacles, n_steps, nom_so, nom_st, unit_begin,
+                            unit_count, n_samples, 0.0, 0.0, 0.0, seed, 0, state, true, path_steps,
+                            zero_first_step, ego_path, ego_stride, 0.0, 0.0, 1.0, 0.0, 0.0, out,
+                            status, nullptr, 0, 0, stream, nullptr, &rs, true, metric, selected,
+                            ego_problem_stride, noise, noise_period);
 }
 #else
 extern "C" int drcvar_sampled_launch_plan(int64_t n_samples, int32_t* threads,

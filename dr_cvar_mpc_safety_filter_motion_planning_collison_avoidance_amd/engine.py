@@ -816,6 +816,182 @@ def sampled_halfspaces_route(nominal_path: torch.Tensor, ego_path: torch.Tensor,
     return out, selected
 
 
+@dataclass(frozen=True)
+class NoiseTable:
+    """Noise factors per look-ahead step of a batch (``include/drcvar_loop_noise.h``): ``chol`` is
+    an array of lower Cholesky factors ``(l00, l10, l11)`` shaped ``[H, 3]`` (one schedule for every
+    obstacle), ``[O, H, 3]`` (one per obstacle, shared by the problems) or ``[B, O, H, 3]`` (one
+    per problem and obstacle).  A factor may be zero, singular or infinite, never NaN."""
+
+    chol: object
+
+    def _array(self):
+        import numpy as np
+        c = np.ascontiguousarray(np.asarray(self.chol, dtype=np.float64))
+        if c.ndim not in (2, 3, 4) or c.shape[-1] != 3 or any(d < 1 for d in c.shape):
+            raise ValueError("chol must have shape [H, 3], [O, H, 3] or [B, O, H, 3] with H >= 1, "
+                             f"got {tuple(c.shape)}")
+        return c
+
+    @classmethod
+    def from_cov(cls, cov) -> "NoiseTable":
+        """The table of the covariances ``cov [..., H, 2, 2]``: each factor formed as
+        ``np.linalg.cholesky`` forms it (what the entries with ``noise_cov`` do)."""
+        import numpy as np
+        cov = np.asarray(cov, dtype=np.float64)
+        if cov.ndim not in (3, 4, 5) or cov.shape[-2:] != (2, 2):
+            raise ValueError(f"cov must have shape [..., H, 2, 2], got {tuple(cov.shape)}")
+        flat = cov.reshape(-1, 2, 2)
+        chol = np.array([_noise_factor(c, None) for c in flat]).reshape(*cov.shape[:-2], 3)
+        return cls(chol)
+
+    @classmethod
+    def scaled(cls, noise_cov, scales) -> "NoiseTable":
+        """``Sigma = scale * noise_cov`` for ``scales [..., H]``; a scale of 1 gives the factor of
+        ``noise_cov`` itself, bit for bit."""
+        import numpy as np
+        scales = np.asarray(scales, dtype=np.float64)
+        base = np.asarray(noise_cov, dtype=np.float64).reshape(2, 2)
+        return cls.from_cov(scales[..., None, None] * base)
+
+    @property
+    def horizon(self) -> int:
+        return int(self._array().shape[-2])
+
+    def validate(self) -> None:
+        import numpy as np
+        if np.isnan(self._array()).any():
+            raise ValueError("a noise factor must not be NaN")
+
+    def period(self, n_problems: int, n_obstacles: int) -> int:
+        """The launch's ``noise_period`` for B problems of O obstacles: 1, O or B O by the table's
+        leading dimensions, which must match."""
+        B, O = int(n_problems), int(n_obstacles)
+        lead = self._array().shape[:-2]
+        if lead == ():
+            return 1
+        if lead == (O,):
+            return O
+        if lead == (B, O):
+            return B * O
+        raise ValueError(f"the noise table's leading dimensions {lead} match neither "
+                         f"n_obstacles={O} nor (n_problems, n_obstacles)={(B, O)}")
+
+    def factor(self, o: int, t: int):
+        """``(l00, l10, l11)`` of global obstacle ``o`` at window step ``t``."""
+        c = self._array()
+        rows = c.reshape(-1, c.shape[-2], 3)
+        return tuple(float(v) for v in rows[int(o) % rows.shape[0], int(t)])
+
+    def to_device(self, device) -> torch.Tensor:
+        """The filled table as a uint8 tensor ``[period * H, row_bytes]`` on ``device``
+        (``drcvar_noise_table_fill`` into host memory, one copy)."""
+        import numpy as np
+        self.validate()
+        c = self._array().reshape(-1, 3)
+        lib = _native.noise_lib()
+        row = int(lib.drcvar_noise_table_row_bytes())
+        host = np.zeros((c.shape[0], row), dtype=np.uint8)
+        _native.check(lib.drcvar_noise_table_fill(c.ctypes.data, c.shape[0], host.ctypes.data,
+                                                  host.nbytes))
+        return torch.from_numpy(host).to(device)
+
+
+def prepare_sampled_halfspaces_noise(nominal_path: torch.Tensor, ego_path: torch.Tensor,
+                                     n_obstacles: int, n_steps: int, n_samples: int,
+                                     params: RiskTable, metric, state: torch.Tensor,
+                                     noise: NoiseTable, *, noise_table: torch.Tensor | None = None,
+                                     draw_period: int | None = None,
+                                     table: torch.Tensor | None = None,
+                                     codes: torch.Tensor | None = None, seed: int = 0,
+                                     zero_first_step: bool = True, unit_begin: int = 0,
+                                     unit_count: int | None = None, out: torch.Tensor | None = None,
+                                     selected: torch.Tensor | None = None,
+                                     status: torch.Tensor | None = None, stream=None
+                                     ) -> tuple[PreparedLaunch, torch.Tensor, torch.Tensor]:
+    """Freeze one ``drcvar_sampled_halfspaces_f64_noise`` call (``include/drcvar_loop_noise.h``):
+    :func:`prepare_sampled_halfspaces_route` whose unit ``(o, t)`` draws with its own factor
+    ``noise.factor(o, t)`` instead of one ``noise_cov`` / ``chol`` per launch.  Returns ``(launch,
+    out, selected)``.
+
+    ``noise`` is a :class:`NoiseTable` whose H is ``n_steps`` and whose leading dimensions match
+    ``n_obstacles`` or ``(B, n_obstacles)``.  For every unit, ``out``, ``status`` and ``selected``
+    hold byte for byte what :func:`prepare_sampled_halfspaces_route` gives with ``chol`` that
+    unit's factor.  ``noise_table`` (optional): ``noise.to_device(device)`` made earlier; the entry
+    cannot check device memory, so it is only accepted with the shape that ``noise`` and the
+    library give it.  Everything else: :func:`prepare_sampled_halfspaces_route` (there is no
+    ``noise_cov`` and no ``chol``)."""
+    if not isinstance(noise, NoiseTable):
+        raise ValueError("noise must be a NoiseTable")
+    noise.validate()
+    if noise.horizon != int(n_steps):
+        raise ValueError(f"the noise table has H={noise.horizon}, the launch n_steps={n_steps}")
+    if not isinstance(ego_path, torch.Tensor) or ego_path.dtype != torch.float64 or \
+            ego_path.dim() != 3 or ego_path.shape[2] != 2 or ego_path.stride(2) != 1:
+        raise ValueError("ego_path must be a float64 [B, P, 2] tensor with adjacent coordinates")
+    if ego_path.stride(0) < 0 or ego_path.stride(1) < 0:
+        raise ValueError("ego_path must not have negative strides")
+    if not isinstance(nominal_path, torch.Tensor) or nominal_path.dim() != 3 or \
+            int(n_obstacles) < 1 or nominal_path.shape[0] % int(n_obstacles) != 0:
+        raise ValueError("nominal_path must be float64 [B O, P, 2] with n_obstacles dividing B O")
+    rows, T = nominal_path.shape[0], int(n_steps)
+    period = noise.period(rows // int(n_obstacles), int(n_obstacles))
+    metric_codes(metric, rows // int(n_obstacles), "cpu")
+    if codes is not None and (not isinstance(codes, torch.Tensor) or codes.dtype != torch.int32
+                              or tuple(codes.shape) != (rows // int(n_obstacles),)
+                              or not codes.is_contiguous()):
+        raise ValueError("codes must be a contiguous int32 [B] tensor (metric_codes)")
+    dev, BO, P, O, B, D, T, n, u0, count, whole, out, table, _ = _risk_launch_setup(
+        nominal_path, ego_path, n_obstacles, n_steps, n_samples, params, state, draw_period, table,
+        DEFAULT_NOISE_COV, unit_begin, unit_count, out, status, None, routes=True)
+    sel_shape = (BO, T, SELECTED_WIDTH) if whole else (count, SELECTED_WIDTH)
+    if selected is None:
+        selected = torch.empty(sel_shape, dtype=torch.float64, device=dev)
+    elif not isinstance(selected, torch.Tensor) or tuple(selected.shape) != sel_shape or \
+            selected.dtype != torch.float64 or not selected.is_contiguous() or selected.device != dev:
+        raise ValueError(f"selected must be a contiguous float64 {list(sel_shape)} tensor on {dev}")
+    if codes is None:
+        codes = metric_codes(metric, B, dev)
+    elif codes.device != dev:
+        raise ValueError(f"codes must live on {dev}")
+    lib = _native.noise_lib()
+    if noise_table is None:
+        noise_table = noise.to_device(dev)
+    row = int(lib.drcvar_noise_table_row_bytes())
+    if not isinstance(noise_table, torch.Tensor) or noise_table.dtype != torch.uint8 or \
+            noise_table.device != dev or tuple(noise_table.shape) != (period * T, row) or \
+            not noise_table.is_contiguous() or noise_table.data_ptr() % 16 != 0:
+        raise ValueError(f"noise_table must be a contiguous, 16-byte aligned uint8 [{period * T}, "
+                         f"{row}] tensor on {dev} (NoiseTable.to_device)")
+    args = (ctypes.c_void_p(nominal_path.data_ptr()), BO, P, nominal_path.stride(0),
+            nominal_path.stride(1), T, u0, count, n, ctypes.c_void_p(noise_table.data_ptr()), period,
+            ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), ctypes.c_void_p(state.data_ptr()),
+            ctypes.c_int32(1 if zero_first_step else 0),
+            ctypes.c_void_p(ego_path.data_ptr()), ego_path.stride(1), ego_path.stride(0), O,
+            ctypes.c_void_p(table.data_ptr()), D, ctypes.c_void_p(codes.data_ptr()),
+            ctypes.c_void_p(out.data_ptr()),
+            ctypes.c_void_p(status.data_ptr() if status is not None else None),
+            ctypes.c_void_p(selected.data_ptr()), ctypes.c_void_p(_stream_handle(dev, stream)))
+    launch = PreparedLaunch(lib.drcvar_sampled_halfspaces_f64_noise, args,
+                            (nominal_path, ego_path, state, table, codes, noise_table, out, status,
+                             selected))
+    return launch, out, selected
+
+
+def sampled_halfspaces_noise(nominal_path: torch.Tensor, ego_path: torch.Tensor, n_obstacles: int,
+                             n_steps: int, n_samples: int, params: RiskTable, metric,
+                             state: torch.Tensor, noise: NoiseTable, **kwargs
+                             ) -> tuple[torch.Tensor, torch.Tensor]:
+    """One ``drcvar_sampled_halfspaces_f64_noise`` launch (arguments:
+    :func:`prepare_sampled_halfspaces_noise`): returns ``(out, selected)``."""
+    launch, out, selected = prepare_sampled_halfspaces_noise(
+        nominal_path, ego_path, n_obstacles, n_steps, n_samples, params, metric, state, noise,
+        **kwargs)
+    if out.numel() > 0:
+        launch()
+    return out, selected
+
+
 def selected_views(selected: torch.Tensor, n_problems: int, n_obstacles: int):
     """``(h [B, O, T, 2], g [B, O, T])``: the solver's halfspace views of a whole-window
     ``selected [B O, T, 4]``, strided, no copy."""

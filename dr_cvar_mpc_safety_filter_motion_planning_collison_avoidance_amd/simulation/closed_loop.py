@@ -800,6 +800,21 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
     dimension is not B is a ``ValueError``; with 2-D paths the batch is what it was, launch for
     launch, and the route library is not loaded.
 
+    ``noise=engine.NoiseTable(...)`` gives every obstacle and look-ahead step its own noise factor
+    (``include/drcvar_loop_noise.h``): ``chol`` is ``[H, 3]``, ``[O, H, 3]`` or
+    ``[B, O, H, 3]`` with H the model's horizon.  Step 1 is then one
+    ``drcvar_sampled_halfspaces_f64_noise`` launch, the route launch whose unit ``(o, t)`` reads its
+    factor from row ``(o mod period) H + t`` of a table on the device; a ``RiskParams`` and a string
+    metric are promoted as routes promote them, 2-D paths run with problem stride 0, and the solve,
+    both advance kernels and the evaluation launch are untouched.  ``noise_cov`` and ``chol`` are
+    then not read by the halfspaces and must be left at their defaults; ``LoopEvaluation`` keeps
+    its own covariance, so an assumed schedule can be held against a true noise.  The ``reference``
+    backend makes one ``engine.sampled_halfspaces(..., chol=f)`` call per problem and distinct
+    factor and takes the units that carry ``f``.  A table whose H or leading dimensions do not
+    match, ``noise`` with ``linearize="predicted"`` or beside a ``noise_cov`` / ``chol`` is a
+    ``ValueError``; with ``noise=None`` the batch is what it was, launch for launch, and the noise
+    library is not loaded.
+
     ``reset(x0)`` takes ``[B, nx]`` or ``[nx]``.  ``run(n, backend)`` returns ``(states [B, n + 1,
     nx], inputs [B, n, nu], info [B, n, 10])``; backends, log capacity, rebasing, the limit of D
     steps per reset under a disturbance and the treatment of failed solves (a logged step; nothing
@@ -812,16 +827,28 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
                  n_problems, metric="dr_cvar", noise_cov=DEFAULT_NOISE_COV, chol=None, seed=0,
                  zero_first_step=True, max_iter=DEFAULT_MAX_ITER, tol=DEFAULT_TOL, polish=True,
                  options=None, disturbance=None, steps_per_graph=1, evaluate=None,
-                 linearize="reference", relinearize=0, draw_period=None):
+                 linearize="reference", relinearize=0, draw_period=None, noise=None):
         names = check_metric(metric, n_problems, linearize)
         if int(steps_per_graph) < 1:
             raise ValueError(f"steps_per_graph={steps_per_graph} must be at least 1")
         check_evaluate(evaluate)
         check_linearize(linearize, relinearize)
+        if noise is not None:   # a noise factor per obstacle and look-ahead step
+            if not isinstance(noise, engine.NoiseTable):
+                raise ValueError("noise must be an engine.NoiseTable or None")
+            if linearize == "predicted":
+                raise ValueError('a NoiseTable cannot be combined with linearize="predicted"')
+            if chol is not None or noise_cov is not DEFAULT_NOISE_COV:
+                raise ValueError("with noise= the halfspaces ignore noise_cov and chol: leave them "
+                                 "at their defaults")
+            noise.validate()
+            if noise.horizon != model.horizon:
+                raise ValueError(f"the NoiseTable has H={noise.horizon}, the model's horizon is "
+                                 f"{model.horizon}")
         # a route per problem: either reference path is [B, P, .]
         routes = any(isinstance(t, torch.Tensor) and t.dim() == 3 for t in (x_ref_path, u_ref_path))
-        if routes and names is None and linearize == "reference":
-            # the route launch is a metric launch: B equal codes
+        if (routes or noise is not None) and names is None and linearize == "reference":
+            # the route launch (and the noise launch, a route launch) is a metric launch: B equal codes
             if int(n_problems) < 1:
                 raise ValueError(f"n_problems={n_problems} must be at least 1")
             names = (metric,) * int(n_problems)
@@ -840,6 +867,8 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         H, nx, nu = model.horizon, model.nx, model.nu
         B = int(n_problems)
         O, P = check_batch_shapes(nominal_path, disturbance, B, nx)
+        self.noise = noise
+        self._noise_period = None if noise is None else noise.period(B, O)
         paths = ((x_ref_path, "x_ref_path", nx), (u_ref_path, "u_ref_path", nu))
         for t, name, _ in paths:   # (both, before either's device is looked at)
             if isinstance(t, torch.Tensor) and t.dim() == 3 and t.shape[0] != B:
@@ -896,6 +925,8 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         if names is not None:
             self._codes = engine.metric_codes(names, B, dev)
             self._selected = torch.zeros((B * O, H, engine.SELECTED_WIDTH), **f64)
+        # a NoiseTable: its rows on the device, copied once (without one the library is not loaded)
+        self._noise_rows = noise.to_device(dev) if noise is not None else None
         self._logs = None           # (x_log [B, cap + 1, nx], u_log [B, cap, nu], info_log [B, cap, 10])
         self._cap, self._step_begin = 0, 0
         self._primed = False
@@ -969,6 +1000,16 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         if self.linearize == "predicted":
             halfspaces = self._lin_launch(stream, 1)
             again = self._lin_launch(stream, 0) if self.relinearize else None
+        elif self.noise is not None:
+            # the route launch with each unit's own factor; 2-D paths run with problem stride 0
+            ego = self.ego_path if self.routes else \
+                self.ego_path.expand(self.n_problems, self.path_steps, 2)
+            halfspaces, _, _ = engine.prepare_sampled_halfspaces_noise(
+                self.nominal_path, ego, self.n_obstacles, H, self.n_samples, self.params,
+                self.metrics, self._state[0], self.noise, noise_table=self._noise_rows,
+                draw_period=self.draw_period, table=self._risk_table, codes=self._codes,
+                seed=self.seed, zero_first_step=self.zero_first_step, out=self._record,
+                selected=self._selected, stream=stream)
         elif self._codes is not None:
             prepare = engine.prepare_sampled_halfspaces_route if self.routes else \
                 engine.prepare_sampled_halfspaces_metric
@@ -1059,6 +1100,31 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
                 zero_first_step=self.zero_first_step, unit_begin=r * O * H, unit_count=O * H))
         return torch.cat(records).view(B * O, H, engine.OUT_WIDTH)
 
+    def _noise_reference_record(self, window, ego_window):
+        """The record ``[B O, H, 8]`` of a NoiseTable batch from the entry that predates the table:
+        :meth:`_risk_reference_record`'s call once per problem and distinct factor ``f`` of that
+        problem's units, with ``chol=f``, from which the units that carry ``f`` are taken."""
+        H, B, O, D = self.model.horizon, self.n_problems, self.n_obstacles, self.draw_period
+        records = []
+        for b in range(B):
+            r = b % D
+            nominal = torch.zeros(((r + 1) * O, H, 2), dtype=torch.float64, device=window.device)
+            nominal[r * O:].copy_(window[b * O:(b + 1) * O])
+            carriers = {}
+            for o in range(O):
+                for t in range(H):
+                    carriers.setdefault(self.noise.factor(b * O + o, t), []).append(o * H + t)
+            record = torch.empty((O * H, engine.OUT_WIDTH), dtype=torch.float64, device=window.device)
+            for f, units in carriers.items():
+                part = engine.sampled_halfspaces(
+                    nominal, ego_window[b] if ego_window.dim() == 3 else ego_window, self.n_samples,
+                    self.params.row(b), chol=f, seed=self.seed, stream_offset=self._offset,
+                    zero_first_step=self.zero_first_step, unit_begin=r * O * H, unit_count=O * H)
+                idx = torch.tensor(units, device=window.device)
+                record[idx] = part[idx]
+            records.append(record)
+        return torch.cat(records).view(B * O, H, engine.OUT_WIDTH)
+
     def _reference_selected(self, record):
         """``[B O, H, 4]``: each problem's ``METRIC_COLUMNS`` gathered from ``record`` with torch
         indexing, the fourth column zero (what the metric launch stores beside the record)."""
@@ -1079,6 +1145,8 @@ class RecedingHorizonBatch(_Evaluated, _Linearized):
         for p in range(1 + self.relinearize):
             if self.linearize == "predicted":
                 record = self._lin_reference_record(window, 1 if p == 0 else 0)
+            elif self.noise is not None:
+                record = self._noise_reference_record(window, self._window(self.ego_path, s, H))
             elif self._risk_table is not None:
                 record = self._risk_reference_record(window, self._window(self.ego_path, s, H))
             else:
